@@ -15,8 +15,16 @@ view v on rank v mod N -- 8 views on one GPU, 1 view + the all-reduce per GPU at
 and N=8 lines describe the same 8-view step.  `--views-per-rank K` (weak scaling): K views per
 rank at every N, the same K at N=1.
 
-Run: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no WORLD_SIZE in the
-environment, this process runs the PMC passes (rank 0's workload) and then starts
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  A plain run
+sets up, warms up, times the K steps, writes the last timed step's outputs if --dump-outputs is
+given, and prints the result line.  Everything else the benchmark measures -- the per-kernel HIP
+event timings and roofline, the rocprofv3 PMC passes, the CPU baselines, the SURVEY §8f side
+measurements (aux), the config2_single_view leg, the workload's geometry (num_rendered, visible)
+and, at N > 1, the all-reduce's share of the step -- runs only with --full (where the --no-*
+options switch its parts off one by one).
+
+With N > 1 and no WORLD_SIZE in the
+environment, this process runs the PMC passes (rank 0's workload; --full only) and then starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a child (it never
 touches the GPU itself, and never re-execs), relays rank 0's JSON line and exits with the child's
 code; under an external torch.distributed.run WORLD_SIZE must equal N.  One rank per GPU over RCCL
@@ -66,6 +74,13 @@ def parse(argv=None):
     ap.add_argument("--views-per-rank", type=int, default=0,
                     help="> 0: weak scaling, this many views per rank at every N (overrides --views-total)")
     ap.add_argument("--antialiasing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: per-kernel timings and roofline, PMC passes, CPU "
+                         "baselines, aux, the single-view leg, geometry, the all-reduce share (off by default: "
+                         "a plain run times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (images, radii, "
+                         "gradients) as DIR/<name>.npy (float32; a fixed seeded sample of the larger arrays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every usable host core (affinity mask, bounded by a cgroup CPU quota)")
@@ -150,6 +165,27 @@ def algorithmic_bytes(P, M, L, N, T, P_vis, views_per_bwd=1, diff_cells=0):
     }
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of a larger output: 9 arrays x 4 MiB, well inside 64 MB per dump
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller (name -> tensor, None
+    skipped), each as path/<name>.npy, flat, float32.  Of an array above DUMP_SAMPLE elements a
+    fixed sample is kept: flat indices drawn from a seed-0 CPU generator in the order of `arrays`,
+    so two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator().manual_seed(0)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def lib_sha256():
     """Identity of the native library this process rasterizes with (stamps PMC traffic figures)."""
     import diff_gaussian_rasterization as dgr
@@ -226,7 +262,7 @@ def single_view_leg(args, timeout=400):
     forward + full backward of view 0 per step (bench.py --views-total 1 --per-view --no-deferred),
     its own per-kernel times, roofline and PMC traffic, in a child process."""
     cmd = [sys.executable, os.path.abspath(__file__), "--views-total", "1", "--per-view", "--no-deferred",
-           "--no-aux", "--no-cpu-baseline", "--no-single-view", "--steps", str(max(args.steps, 20)),
+           "--full", "--no-aux", "--no-cpu-baseline", "--no-single-view", "--steps", str(max(args.steps, 20)),
            "--warmup", str(args.warmup), "--P", str(args.P), "--width", str(args.width),
            "--height", str(args.height)] + (["--antialiasing"] if args.antialiasing else []) \
         + (["--no-pmc"] if args.no_pmc else []) + (["--no-profile"] if args.no_profile else [])
@@ -314,6 +350,8 @@ def rank_views(args, rank, views_world):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if not args.full:  # a plain run: the timed steps and the result line, none of the side measurements
+        args.no_profile = args.no_pmc = args.no_cpu_baseline = args.no_aux = args.no_single_view = True
     env_world = os.environ.get("WORLD_SIZE")
     if not args.pmc_child:
         if env_world is None and args.gpus > 1:
@@ -408,7 +446,12 @@ def main(argv=None):
     # next computes) unless --no-overlap-allreduce; comm=False: no collective (compute-only pass)
     overlap_ar = world > 1 and not args.no_overlap_allreduce and (args.batch_views or args.deferred)
 
-    def step(record_allreduce=False, overlap=True, comm=True):
+    last = {}  # --dump-outputs: what the last timed step returned to its caller
+
+    def step(record_allreduce=False, overlap=True, comm=True, keep=False):
+        last["keep"] = keep
+        if keep:
+            last["views"] = []
         for p in params.values():
             p.grad = None
         for m in means2Ds:
@@ -420,6 +463,8 @@ def main(argv=None):
                 color, radii, inv = mv(means3D=params["means3D"], means2D=means2D_batch, shs=params["shs"],
                                        opacities=params["opacities"], scales=params["scales"],
                                        rotations=params["rotations"])
+                if keep:
+                    last["views"] = [(color, radii, inv)]
                 torch.autograd.backward([color, inv], [gc_batch, gi_batch])
             else:
                 n_st = len(streams) if overlap else 1
@@ -448,6 +493,8 @@ def main(argv=None):
                     color, radii, inv = rast(means3D=params["means3D"], means2D=means2Ds[i], shs=params["shs"],
                                              opacities=params["opacities"], scales=params["scales"],
                                              rotations=params["rotations"])
+            if last["keep"]:
+                last["views"].append((color.unsqueeze(0), radii.unsqueeze(0), inv.unsqueeze(0)))
             return st, color, inv
 
         def backward(i, out):
@@ -499,7 +546,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        step()
+        step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -508,6 +555,16 @@ def main(argv=None):
     elapsed = multiview.max_over_ranks(t1 - t0, dev)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     median_ms = multiview.max_over_ranks(statistics.median(step_ms) / 1e3, dev) * 1e3
+
+    if args.dump_outputs and rank == 0 and last.get("views"):
+        m2d = means2D_batch.grad if mv is not None else (
+            torch.stack([m.grad for m in means2Ds]) if all(m.grad is not None for m in means2Ds) else None)
+        arrays = {name: torch.cat([o[k] for o in last["views"]])
+                  for k, name in enumerate(("color", "radii", "invdepth"))}
+        arrays.update({"grad_" + k: p.grad for k, p in params.items()})
+        arrays["grad_means2D"] = m2d
+        dump_outputs(args.dump_outputs, arrays)
+    last.clear()
 
     # per-kernel HIP-event timings: a second, instrumented run of the same steps (the events
     # recorded around every launch cost ~3% of the step, so they stay out of the timed region)
@@ -534,7 +591,7 @@ def main(argv=None):
     # a non-overlapped allreduce_grads), and the step without any collective (compute only); the
     # exposed communication is the timed step minus the compute-only step
     allreduce = None
-    if world > 1:
+    if world > 1 and args.full:
         for _ in range(min(args.steps, 5)):
             step(record_allreduce=True)
         torch.cuda.synchronize()
@@ -560,15 +617,15 @@ def main(argv=None):
     # geometry of the workload (one extra forward per view outside the timed region)
     with torch.no_grad():
         Ls, vis = [], []
-        for s in cams:  # per-view geometry, averaged like the per-kernel times are
+        for s in (cams if args.full else []):  # per-view geometry, averaged like the per-kernel times are
             out = dgr._C.rasterize_gaussians(s.bg, params["means3D"], torch.Tensor([]), params["opacities"],
                                              params["scales"], params["rotations"], 1.0, torch.Tensor([]),
                                              s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, H, W, params["shs"], 3,
                                              s.campos, False, args.antialiasing, False)
             Ls.append(int(out[0]))
             vis.append(int((out[2] > 0).sum().item()))
-        L = round(sum(Ls) / len(Ls))
-        P_vis = round(sum(vis) / len(vis))
+        L = round(sum(Ls) / len(Ls)) if Ls else None
+        P_vis = round(sum(vis) / len(vis)) if vis else None
     N = H * W
     T = ((W + 15) // 16) * ((H + 15) // 16)
     pix_total = views_step * N * args.steps
@@ -680,6 +737,7 @@ def main(argv=None):
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         # the median of the steps' stream times (events at the step boundaries, max over ranks)
         "ms_per_step": round(median_ms, 4),
         "ms_per_step_median": round(median_ms, 4),

@@ -83,6 +83,73 @@ def test_rccl_needs_enough_gpus():
     assert r.returncode == 2 and "needs 2 GPUs" in r.stderr
 
 
+def test_dump_outputs_writes_fixed_float32_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy, flat float32; above DUMP_SAMPLE elements the same
+    seeded sample in every run; an absent array (None) is skipped."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    big = torch.arange(3 * 7 * 11, dtype=torch.float32).reshape(3, 7, 11)
+    arrays = {"color": big, "radii": torch.arange(10, dtype=torch.int32), "grad_means2D": None,
+              "grad_shs": -big.double()}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("color", "radii", "grad_shs")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["color.npy", "grad_shs.npy", "radii.npy"]
+    assert all(v.dtype == np.float32 and v.ndim == 1 for v in a.values())
+    assert np.array_equal(a["radii"], np.arange(10)) and a["color"].size == a["grad_shs"].size == 100
+    # the sampled values are elements of the array (an arange: each value is its own flat index)
+    assert (a["color"] == np.round(a["color"])).all() and a["color"].min() >= 0 and a["color"].max() < big.numel()
+    assert len(set(a["color"].tolist())) > 50 and (a["grad_shs"] <= 0).all()
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / (n + ".npy")))
+
+
+SMALL = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--P", "5000", "--width", "200", "--height", "120"]
+FULL_ONLY = ("roofline", "cpu_baseline", "aux", "allreduce")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--per-view"]], ids=["batch", "per-view"])
+def test_plain_run_is_lean_and_dumps_outputs(extra, tmp_path):
+    """A plain run times the steps and prints the result line with none of the --full legs; with
+    --dump-outputs it writes the last timed step's images, radii and gradients, finite and of the
+    step's sizes (8 views of 5000 Gaussians at 200x120; shs: 16 x 3 floats per Gaussian)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL + extra + ["--dump-outputs", str(out)],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=200)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = lines[0]
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert all(d[k] is None for k in FULL_ONLY) and d.get("config2_single_view") is None
+    V, P, N = 8, 5000, 200 * 120
+    sizes = {"color": V * 3 * N, "invdepth": V * N, "radii": V * P, "grad_means3D": P * 3, "grad_scales": P * 3,
+             "grad_rotations": P * 4, "grad_opacities": P, "grad_shs": P * 48, "grad_means2D": V * P * 3}
+    assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in sizes)
+    for n, size in sizes.items():
+        a = np.load(out / (n + ".npy"))
+        assert a.dtype == np.float32 and a.size == size and np.isfinite(a).all() and np.count_nonzero(a) > 0, n
+
+
+@pytest.mark.gpu
+def test_full_run_measures_the_side_legs():
+    """--full: the per-kernel pass and the geometry run again (the PMC passes, CPU baselines, aux and
+    single-view legs switched off one by one here, as the --no-* options allow)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL
+                       + ["--full", "--no-pmc", "--no-cpu-baseline", "--no-aux", "--no-single-view"],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=200)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+    assert d["full"] is True and d["steps"] == 2 and d["ms_per_step"] > 0
+    assert {"render_fwd", "render_bwd", "preprocess_bwd"} <= set(d["roofline"]["kernels"])
+    assert d["config"]["num_rendered"] > 0 and 0 < d["config"]["visible"] <= 5000
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["strong", "weak"])
 def test_gpus2_gloo_rehearsal_on_one_gpu(mode):

@@ -7,6 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=${1:-2}
 KS=${2:-render_fwd,render_bwd,preprocess_bwd,preprocess_fwd,depth_sort,tile_sort}
 LIB=gaussian-splatting-npu_amd/diff_gaussian_rasterization/libgsr_hip.so
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"  # the per-kernel averages printed below come from the --full legs
 cp "$LIB" /tmp/lib_orig.so
 mkdir -p gpurun_out/ab
 for r in $(seq "$R"); do

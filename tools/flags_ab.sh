@@ -10,6 +10,7 @@ for r in $(seq "$R"); do
   i=0
   for f in "$@"; do
     i=$((i+1))
+    f="--full $f"  # the per-kernel averages printed below come from the --full legs
     timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-aux --no-pmc $f > "gpurun_out/fab/$i.$r.log" 2>&1 || { tail -5 "gpurun_out/fab/$i.$r.log"; exit 1; }
     python3 - "gpurun_out/fab/$i.$r.log" "$f" <<'PY'
 import json, sys

@@ -28,6 +28,6 @@ step() {  # step <name> <timeout> <cmd...>
 step build 600 python -c "import __graft_entry__ as g; g.build()"
 step pytest_gpu 900 python -m pytest tests -m gpu -x -q "$@"
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps 10 --warmup 3
-step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-profile
+step bench 600 python bench.py --full --steps 10 --warmup 3
+step rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-profile
 echo "session done"

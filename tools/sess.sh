@@ -34,9 +34,9 @@ for st in "$@"; do
     testsel:*) run pytest_sel 600 python -u -m pytest ${st#testsel:} -m gpu -x -v --timeout 300 --timeout-method thread
           cp -f gpurun_out/parity_stats.json "$OUT/" 2>/dev/null ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python -u bench.py
+    bench) run bench 600 python -u bench.py --full
            cp -f gpurun_out/pmc_step.json gpurun_out/pmc_single.json "$OUT/" 2>/dev/null ;;
-    benchq) run benchq 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-aux --no-pmc --no-single-view ;;
+    benchq) run benchq 300 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-aux --no-pmc --no-single-view ;;
     trace) run trace 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-aux --no-single-view --no-pmc
            python3 - "$OUT" <<'PY'
 import csv, glob, sys
