@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -34,7 +35,7 @@ constexpr uint32_t L_PENDING = 0xFFFFFFFFu;  // h[2] before the scan stores num_
 constexpr int GSR_RERUN_WIDE = -100;
 // depth-sort passes of this thread's last forward (per view: 3, or 4 after a re-run of its depth
 // sort; gsr_debug_last_depth_passes)
-thread_local int t_last_depth_passes[16] = {};
+thread_local int t_last_depth_passes[MAX_VIEWS] = {};
 
 int fail(int code, const char* msg)
 {
@@ -91,9 +92,7 @@ int pinned(int slot, uint32_t** out)
 // ---------------------------------------------------------------------------
 // the fork / join events order streams of one device only: no system-scope fence (the host never
 // inspects them; what the host reads -- num_rendered -- the scan stores with system-scope atomics)
-#ifndef GSR_EVENT_FLAGS
-#define GSR_EVENT_FLAGS (hipEventDisableTiming | hipEventDisableSystemFence)
-#endif
+constexpr unsigned EVENT_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence;
 constexpr int PREFIX_STREAMS = 4;  // views whose binning prefixes run side by side (gsr_forward_views)
 struct PrefixStream {
     hipStream_t s[PREFIX_STREAMS] = {};
@@ -107,10 +106,7 @@ thread_local PrefixStream g_prefix[MAX_DEVICES];
 // gsr_set_prefix_stream: 0 = everything on the caller's stream; 1 = the prefix on its own
 // high-priority stream (forked from the caller's, joined before render_fwd) and its side work on
 // the auxiliary stream; 2 = the prefix on the caller's stream, its side work on the auxiliary stream
-#ifndef GSR_PREFIX_MODE_DEFAULT
-#define GSR_PREFIX_MODE_DEFAULT 1
-#endif
-thread_local int g_prefix_mode = GSR_PREFIX_MODE_DEFAULT;
+thread_local int g_prefix_mode = 1;
 
 // n (<= PREFIX_STREAMS) prefix streams of the current device, each forked from `caller`; all of
 // them the caller's own stream when the prefix streams are off (or the device is out of range).
@@ -124,8 +120,8 @@ int prefix_fork(hipStream_t caller, int n, hipStream_t* out)
     if (dev < 0 || dev >= MAX_DEVICES) return GSR_OK;
     PrefixStream& ps = g_prefix[dev];
     if (!ps.fork) {
-        if ((e = hipEventCreateWithFlags(&ps.fork, GSR_EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.join, GSR_EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
+        if ((e = hipEventCreateWithFlags(&ps.fork, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
+        if ((e = hipEventCreateWithFlags(&ps.join, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
     }
     if ((e = hipEventRecord(ps.fork, caller)) != hipSuccess) return fail_hip(e, __LINE__);
     for (int k = 0; k < n; k++) {
@@ -165,8 +161,8 @@ int aux_fork(hipStream_t s, hipStream_t* out)
         if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return fail_hip(e, __LINE__);
         if ((e = hipStreamCreateWithPriority(&ps.aux, hipStreamNonBlocking, greatest)) != hipSuccess)
             return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.aux_in, GSR_EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.aux_out, GSR_EVENT_FLAGS)) != hipSuccess)
+        if ((e = hipEventCreateWithFlags(&ps.aux_in, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
+        if ((e = hipEventCreateWithFlags(&ps.aux_out, EVENT_FLAGS)) != hipSuccess)
             return fail_hip(e, __LINE__);
     }
     if ((e = hipEventRecord(ps.aux_in, s)) != hipSuccess) return fail_hip(e, __LINE__);
@@ -248,6 +244,17 @@ struct ProfScope {
     int k; hipStream_t s; hipEvent_t e; bool part;
     ProfScope(int k_, hipStream_t s_, bool part_ = false) : k(k_), s(s_), e(prof_begin(k_, s_)), part(part_) {}
     ~ProfScope() { prof_end(k, s, e, part); }
+};
+
+// The tile grid of a width x height image: tiles per row and column, and their number.
+struct TileGrid {
+    uint32_t gx, gy;
+    int T;
+    TileGrid(int width, int height)
+        : gx((uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X)), gy((uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y)),
+          T((int)(gx * gy))
+    {
+    }
 };
 
 template <typename T>
@@ -380,8 +387,9 @@ static int forward_geometry_args(char* geometry_buffer, char* image_buffer, int 
     a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
     a.focal_y = height / (2.0f * tan_fovy);
     a.focal_x = width / (2.0f * tan_fovx);
-    a.grid_x = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    a.grid_y = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
+    const TileGrid tg(width, height);
+    a.grid_x = tg.gx;
+    a.grid_y = tg.gy;
     a.prefiltered = prefiltered; a.antialiasing = antialiasing;
     a.radii = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
     a.means2D = at<float>(gb, g.off[GEOM_MEANS2D]);
@@ -419,16 +427,36 @@ static int forward_geometry_args(char* geometry_buffer, char* image_buffer, int 
 // The forward tile order of a view whose tile ranges come from the rects' difference array
 // (tile_hist): it needs nothing from the tile sort, so it runs on the auxiliary stream right after
 // tile_hist, beside the depth and tile sorts, instead of between the tile sort and render_fwd.
-static OrderJob diff_order_job(char* ib, int width, int height, uint32_t gx, uint32_t gy)
+static OrderJob diff_order_job(char* ib, int width, int height)
 {
     const ImageLayout im = image_layout(width, height);
+    const TileGrid tg(width, height);
     OrderJob oj = {};
     oj.order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
     oj.diff = at<int>(ib, im.off[IMG_TILE_DIFF]);
     oj.ranges_out = at<uint2>(ib, im.off[IMG_RANGES]);
-    oj.grid_x = gx;
-    oj.grid_y = gy;
+    oj.grid_x = tg.gx;
+    oj.grid_y = tg.gy;
     return oj;
+}
+
+// A view's depth sort (the first half of the reference's tile|depth key sort): the keys preprocess
+// wrote, ping-pong buffers carved from GEOM_DSORT_TMP; the last pass also lays the tile rects and tile
+// counts out in depth order (the counts into point_offsets, which the scan then turns into offsets in
+// place).  h_dev: the view's pinned words (word 1: the "range too wide" flag).
+static SortJob depth_sort_job(char* gb, const PreprocessArgs& a, uint32_t* h_dev)
+{
+    const GeomLayout g = geom_layout(a.P);
+    char* tmp = gb + g.off[GEOM_DSORT_TMP];
+    const size_t q = align_up(4 * (size_t)a.P, 256);
+    // keys u32, payload u32x2 (id, packed rect): k0 | v0 v0 | k1 | v1 v1
+    SortJob j = {a.P, a.dkey, nullptr, at<uint32_t>(tmp, 0), at<uint32_t>(tmp, q), at<uint32_t>(tmp, 3 * q),
+                 at<uint32_t>(tmp, 4 * q), at<uint32_t>(gb, g.off[GEOM_SORTED_IDS]), nullptr, nullptr,
+                 gb + g.off[GEOM_RADIX_SCRATCH], a.rect, at<uint2>(gb, g.off[GEOM_SORTED_RECT]),
+                 at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]), a.rect4};
+    j.host_wide = h_dev + 1;
+    j.gsum_zeroed = true;  // (preprocess)
+    return j;
 }
 
 // After preprocess: the record-slot scan, the depth sort and the tile-count scan of one view.
@@ -458,30 +486,15 @@ static int forward_geometry_sort(const PreprocessArgs& a, char* gb, char* ib, in
     }
     if (e == hipSuccess && a.tile_diff) {  // ... and from it the tile ranges and the forward's tile order
         ProfScope ps_(PK_TILE_ORDER, aux);
-        const OrderJob oj = diff_order_job(ib, width, height, a.grid_x, a.grid_y);
+        const OrderJob oj = diff_order_job(ib, width, height);
         e = launch_tile_order_batch(&oj, 1, (int)(a.grid_x * a.grid_y), aux);
     }
 
-    // 2. stable depth sort of the Gaussians (first half of the reference's tile|depth key sort)
-    uint32_t* sorted_ids = at<uint32_t>(gb, g.off[GEOM_SORTED_IDS]);
+    // 2. stable depth sort of the Gaussians
     if (e == hipSuccess) {
-        char* tmp = gb + g.off[GEOM_DSORT_TMP];
-        const size_t q = align_up(4 * (size_t)P, 256);
-        // keys u32, payload u32x2 (id, packed rect): k0 | v0 v0 | k1 | v1 v1
-        uint32_t* k0 = reinterpret_cast<uint32_t*>(tmp);
-        uint32_t* v0 = reinterpret_cast<uint32_t*>(tmp + q);
-        uint32_t* k1 = reinterpret_cast<uint32_t*>(tmp + 3 * q);
-        uint32_t* v1 = reinterpret_cast<uint32_t*>(tmp + 4 * q);
         ProfScope ps_(PK_DEPTH_SORT, s);
-        // the last pass also lays the tile rects and tile counts out in depth order (the counts
-        // into point_offsets, which the scan then turns into offsets in place)
-        SortJob j = {P, a.dkey, nullptr, k0, v0, k1, v1, sorted_ids, nullptr, nullptr, gb + g.off[GEOM_RADIX_SCRATCH],
-                     a.rect, at<uint2>(gb, g.off[GEOM_SORTED_RECT]), at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]),
-                     a.rect4};
-        j.host_wide = h_dev + 1;
-        j.gsum_zeroed = true;  // (preprocess)
-        *dsort_out = j;
-        e = radix_sort_batch(&j, 1, DEPTH_BITS, s);
+        *dsort_out = depth_sort_job(gb, a, h_dev);
+        e = radix_sort_batch(dsort_out, 1, DEPTH_BITS, s);
     }
     if (debug && e == hipSuccess) e = hipStreamSynchronize(s);
 
@@ -579,7 +592,24 @@ static int depth_sort_rerun_wide(SortJob* dsort, const ScanJob* off, uint32_t* c
     return GSR_OK;
 }
 
-int gsr_debug_last_depth_passes(int view) { return view >= 0 && view < 16 ? t_last_depth_passes[view] : 0; }
+// The single view's hand-off: waits for L; after a depth range too wide for three passes, this call's
+// depth sort runs again in four, `recount` (if any) enqueues again what the caller had put behind the
+// scan, and L is awaited once more.
+static int forward_geometry_wait_rerun(uint32_t* h, SortJob* dsort, const ScanJob* off, hipStream_t ps, int* L,
+                                       const std::function<int()>& recount)
+{
+    int rc = forward_geometry_wait(h, ps, L);
+    t_last_depth_passes[0] = depth_force_wide() ? 4 : 3;
+    if (rc == GSR_RERUN_WIDE) {
+        rc = depth_sort_rerun_wide(dsort, off, &h, 1, ps);
+        if (!rc && recount) rc = recount();
+        if (!rc) rc = forward_geometry_wait(h, ps, L);
+        t_last_depth_passes[0] = 4;
+    }
+    return rc;
+}
+
+int gsr_debug_last_depth_passes(int view) { return view >= 0 && view < MAX_VIEWS ? t_last_depth_passes[view] : 0; }
 
 int gsr_debug_grad_record_floats(void) { return GRAD_REC; }
 
@@ -604,13 +634,7 @@ int gsr_forward_geometry_dc(char* geometry_buffer, char* image_buffer, int P, in
                                  viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, antialiasing,
                                  radii, debug, ps, &h, &dsort, &off);
     if (rc) return rc;
-    rc = forward_geometry_wait(h, ps, num_rendered);
-    t_last_depth_passes[0] = depth_force_wide() ? 4 : 3;
-    if (rc == GSR_RERUN_WIDE) {  // this call only: the depth sort in four passes
-        rc = depth_sort_rerun_wide(&dsort, &off, &h, 1, ps);
-        if (!rc) rc = forward_geometry_wait(h, ps, num_rendered);
-        t_last_depth_passes[0] = 4;
-    }
+    rc = forward_geometry_wait_rerun(h, &dsort, &off, ps, num_rendered, nullptr);
     const int rj = prefix_end((hipStream_t)stream, ps);
     return rc ? rc : rj;
 }
@@ -636,10 +660,9 @@ static TileSortJob fused_tile_sort_job(char* gb, char* bb, char* ib, int P, int 
     j.sorted_ids = at<uint32_t>(gb, g.off[GEOM_SORTED_IDS]);
     j.offsets = at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]);
     j.sorted_rects = at<uint2>(gb, g.off[GEOM_SORTED_RECT]);
-    j.rec_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
     j.pass1_scratch = gb + g.off[GEOM_DSORT_TMP];
-    const bool diff = use_tile_diff((uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X),
-                                    (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y));
+    const TileGrid tg(width, height);
+    const bool diff = use_tile_diff(tg.gx, tg.gy);
     // with the difference array the tile order writes every range and nothing reads the sorted
     // tile ids: no clearing of the ranges, no tile id written per instance
     j.ranges = diff ? nullptr : at<uint2>(ib, im.off[IMG_RANGES]);
@@ -650,8 +673,7 @@ static TileSortJob fused_tile_sort_job(char* gb, char* bb, char* ib, int P, int 
     j.v0 = reinterpret_cast<uint32_t*>(w + 4 * q);  // u32x2 payloads
     j.v1 = reinterpret_cast<uint32_t*>(w + 6 * q);
     j.scratch = bb + b.off[BIN_RADIX_SCRATCH];
-    j.slotless = slots_from_rect((uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X),
-                                 (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y));
+    j.slotless = slots_from_rect(tg.gx, tg.gy);
     j.out_slot = j.slotless ? nullptr : at<uint32_t>(bb, b.off[BIN_SLOT]);
     j.out_ids = at<uint32_t>(bb, b.off[BIN_POINT_LIST]);
     j.out_tiles = diff ? nullptr : at<uint32_t>(bb, b.off[BIN_SORTED_TILES]);
@@ -685,7 +707,7 @@ static RenderFwdArgs render_fwd_args(char* gb, char* bb, char* ib, int P, int L,
     r.tile_work = at<uint32_t>(ib, im.off[IMG_TILE_WORK]);
     r.point_list = L > 0 ? at<uint32_t>(bb, b.off[BIN_POINT_LIST]) : nullptr;
     r.W = width; r.H = height;
-    r.grid_x = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
+    r.grid_x = TileGrid(width, height).gx;
     r.splat = at<float4>(gb, g.off[GEOM_SPLAT]);
     r.bg = background;
     r.final_T = at<float>(ib, im.off[IMG_FINAL_T]);
@@ -714,31 +736,29 @@ static int forward_render_impl(char* geometry_buffer, char* binning_buffer, char
     char* ib = image_buffer;
     char* bb = binning_buffer;
     if (L > 0 && !bb) return fail(GSR_ERR_ALLOC, "null binning buffer");
-    const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    const uint32_t gy = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    const int T = (int)(gx * gy);
+    const TileGrid tg(width, height);
     uint32_t* sorted_tiles = L > 0 ? at<uint32_t>(bb, b.off[BIN_SORTED_TILES]) : nullptr;
     if (L > 0) {
         // stable sort by tile id over bits [0, msb(T)) of the depth-ordered instances
         // (rasterizer_impl.cu:303-311 sorts [0, 32 + msb(T)) of the tile|depth keys)
         const TileSortJob j = fused_tile_sort_job(gb, bb, ib, P, L, width, height);
         ProfScope ps_(PK_TILE_SORT, s, counted);
-        HIP_TRY(tile_sort_fused_batch(&j, 1, gx, T, s, counted ? FUSED_SCATTER : FUSED_ALL));
+        HIP_TRY(tile_sort_fused_batch(&j, 1, tg.gx, tg.T, s, counted ? FUSED_SCATTER : FUSED_ALL));
     }
     DEBUG_SYNC(s);
     uint2* ranges = at<uint2>(ib, im.off[IMG_RANGES]);
     uint32_t* tile_order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
-    if (use_tile_diff(gx, gy)) {
+    if (use_tile_diff(tg.gx, tg.gy)) {
         // ranges and order: written from the rects' difference array by the geometry half (the
         // auxiliary stream, joined before the tile-count scan)
     } else {
         {
             ProfScope ps_(PK_RANGES, s);
-            HIP_TRY(launch_tile_ranges(L, sorted_tiles, ranges, T, s));
+            HIP_TRY(launch_tile_ranges(L, sorted_tiles, ranges, tg.T, s));
         }
         DEBUG_SYNC(s);
         ProfScope ps_(PK_TILE_ORDER, s);
-        HIP_TRY(launch_tile_order(ranges, nullptr, T, tile_order, s));
+        HIP_TRY(launch_tile_order(ranges, nullptr, tg.T, tile_order, s));
     }
     {
         const int rc = prefix_end(caller, prefix);
@@ -748,7 +768,7 @@ static int forward_render_impl(char* geometry_buffer, char* binning_buffer, char
     const RenderFwdArgs r = render_fwd_args(gb, bb, ib, P, L, background, width, height, out_color, depth);
     {
         ProfScope ps_(PK_RENDER_FWD, s);
-        HIP_TRY(launch_render_fwd(r, T, s));
+        HIP_TRY(launch_render_fwd(r, tg.T, s));
     }
     DEBUG_SYNC(s);
     return GSR_OK;
@@ -808,11 +828,10 @@ int gsr_forward_prealloc_dc(char* geometry_buffer, char* image_buffer, char* bin
     // the tile sort's first-pass histograms need only the depth-ordered rects and offsets (not L or
     // the binning buffer): enqueued before the read-back, they run while the host waits
     auto count_pass = [&]() -> int {
-        const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-        const int T = (int)(gx * (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y));
+        const TileGrid tg(width, height);
         const TileSortJob cj = fused_tile_sort_job(geometry_buffer, nullptr, image_buffer, P, 0, width, height);
         ProfScope ps_(PK_TILE_SORT, ps);
-        const hipError_t e = tile_sort_fused_batch(&cj, 1, gx, T, ps, FUSED_COUNT);
+        const hipError_t e = tile_sort_fused_batch(&cj, 1, tg.gx, tg.T, ps, FUSED_COUNT);
         return e == hipSuccess ? GSR_OK : fail_hip(e, __LINE__);
     };
     rc = count_pass();
@@ -821,14 +840,7 @@ int gsr_forward_prealloc_dc(char* geometry_buffer, char* image_buffer, char* bin
         return rc;
     }
     int L = 0;
-    rc = forward_geometry_wait(h, ps, &L);
-    t_last_depth_passes[0] = depth_force_wide() ? 4 : 3;
-    if (rc == GSR_RERUN_WIDE) {  // this call only: the depth sort in four passes, then its histograms again
-        rc = depth_sort_rerun_wide(&dsort, &off, &h, 1, ps);
-        if (!rc) rc = count_pass();
-        if (!rc) rc = forward_geometry_wait(h, ps, &L);
-        t_last_depth_passes[0] = 4;
-    }
+    rc = forward_geometry_wait_rerun(h, &dsort, &off, ps, &L, count_pass);  // (a re-run: the histograms again)
     *num_rendered = L;
     if (rc) {
         prefix_end((hipStream_t)stream, ps);
@@ -863,9 +875,7 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
     }
     if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
     hipStream_t caller = (hipStream_t)stream;
-    const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    const uint32_t gy = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    const int T = (int)(gx * gy);
+    const TileGrid tg(width, height);
     const GeomLayout g = geom_layout(P);
     const ImageLayout im = image_layout(width, height);
 
@@ -907,17 +917,9 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
         // each Gaussian's first gradient-record slot (index-order exclusive scan of the tile counts)
         rec[v] = {a.tiles_touched, at<uint32_t>(gb, g.off[GEOM_EMIT_START]), P, a.scan_status + scan_status_words(P),
                   nullptr};
-        char* tmp = gb + g.off[GEOM_DSORT_TMP];
-        const size_t q = align_up(4 * (size_t)P, 256);
-        // keys u32, payload u32x2 (id, packed rect): k0 | v0 v0 | k1 | v1 v1
-        dsort[v] = {P, a.dkey, nullptr, reinterpret_cast<uint32_t*>(tmp), reinterpret_cast<uint32_t*>(tmp + q),
-                    reinterpret_cast<uint32_t*>(tmp + 3 * q), reinterpret_cast<uint32_t*>(tmp + 4 * q),
-                    at<uint32_t>(gb, g.off[GEOM_SORTED_IDS]), nullptr, nullptr, gb + g.off[GEOM_RADIX_SCRATCH], a.rect,
-                    at<uint2>(gb, g.off[GEOM_SORTED_RECT]), at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]), a.rect4};
+        dsort[v] = depth_sort_job(gb, a, hdev[v]);
         uint32_t* offsets = at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]);
         off[v] = {offsets, offsets, P, a.scan_status, hdev[v] + 2};  // L -> the view's pinned word
-        dsort[v].host_wide = hdev[v] + 1;
-        dsort[v].gsum_zeroed = true;  // (preprocess)
     }
     // the record-slot scans (read only by the fused tile sort) on the auxiliary stream, beside the
     // depth sorts
@@ -928,18 +930,18 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
         // every exit after the fork joins the auxiliary stream back first: the caller's stream
         // must stay ordered after what is already queued there (it writes the caller's buffers)
         hipError_t e = launch_scan_batch(rec, V, true, aux);
-        if (e == hipSuccess && use_tile_diff(gx, gy)) {  // the rects' difference arrays, beside the depth sorts
+        if (e == hipSuccess && use_tile_diff(tg.gx, tg.gy)) {  // the rects' difference arrays, beside the depth sorts
             TileHistJob hj[MAX_VIEWS];
             for (int v = 0; v < V; v++) hj[v] = {pa[v].rect4, P, pa[v].tile_diff};
             {
                 ProfScope ps_(PK_RANGES, aux);
-                e = launch_tile_hist_batch(hj, V, gx, gy, aux);
+                e = launch_tile_hist_batch(hj, V, tg.gx, tg.gy, aux);
             }
             if (e == hipSuccess) {  // the views' tile ranges and forward tile orders, beside the sorts
                 OrderJob dj[MAX_VIEWS];
-                for (int v = 0; v < V; v++) dj[v] = diff_order_job(image_buffers[v], width, height, gx, gy);
+                for (int v = 0; v < V; v++) dj[v] = diff_order_job(image_buffers[v], width, height);
                 ProfScope ps_(PK_TILE_ORDER, aux);
-                e = launch_tile_order_batch(dj, V, T, aux);
+                e = launch_tile_order_batch(dj, V, tg.T, aux);
             }
         }
         if (e == hipSuccess) {
@@ -961,7 +963,7 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
         for (int i = 0; i < n; i++)
             cj[i] = fused_tile_sort_job(geometry_buffers[which[i]], nullptr, image_buffers[which[i]], P, 0, width, height);
         ProfScope ps_(PK_TILE_SORT, ps);
-        return tile_sort_fused_batch(cj, n, gx, T, ps, FUSED_COUNT);
+        return tile_sort_fused_batch(cj, n, tg.gx, tg.T, ps, FUSED_COUNT);
     };
     {
         int all[MAX_VIEWS];
@@ -1025,15 +1027,15 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
     }
     if (ns) {
         ProfScope ps_(PK_TILE_SORT, ps, true);
-        HIP_TRY(tile_sort_fused_batch(tsort, ns, gx, T, ps, FUSED_SCATTER));
+        HIP_TRY(tile_sort_fused_batch(tsort, ns, tg.gx, tg.T, ps, FUSED_SCATTER));
     }
-    if (nf && !use_tile_diff(gx, gy)) {  // (with the difference array: ranges and orders are done)
+    if (nf && !use_tile_diff(tg.gx, tg.gy)) {  // (with the difference array: ranges and orders are done)
         {
             ProfScope ps_(PK_RANGES, ps);
-            HIP_TRY(launch_tile_ranges_batch(rj, nf, T, ps));
+            HIP_TRY(launch_tile_ranges_batch(rj, nf, tg.T, ps));
         }
         ProfScope ps_(PK_TILE_ORDER, ps);
-        HIP_TRY(launch_tile_order_batch(oj, nf, T, ps));
+        HIP_TRY(launch_tile_order_batch(oj, nf, tg.T, ps));
     }
     DEBUG_SYNC(ps);
     rc = prefix_end(caller, ps);
@@ -1047,10 +1049,114 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
     }
     if (nf) {  // every view's render in one launch (one launch tail per batch)
         ProfScope ps_(PK_RENDER_FWD, caller);
-        HIP_TRY(launch_render_fwd_batch(ra, nf, T, caller));
+        HIP_TRY(launch_render_fwd_batch(ra, nf, tg.T, caller));
     }
     DEBUG_SYNC(caller);
     return GSR_OK;
+}
+
+// render_bwd's arguments for one view (P, R > 0)
+static RenderBwdArgs render_bwd_args(int P, int R, const float* background, int width, int height, char* gb,
+                                     char* bb, char* ib, const float* dL_dpix, const float* dL_invdepths)
+{
+    const GeomLayout g = geom_layout(P);
+    const ImageLayout im = image_layout(width, height);
+    const BinLayout b = bin_layout(R);
+    const TileGrid tg(width, height);
+    RenderBwdArgs r;
+    r.ranges = at<uint2>(ib, im.off[IMG_RANGES]);
+    r.tile_order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
+    r.tile_work = at<uint32_t>(ib, im.off[IMG_TILE_WORK]);
+    r.point_list = at<uint32_t>(bb, b.off[BIN_POINT_LIST]);
+    r.W = width; r.H = height; r.grid_x = tg.gx;
+    r.T = tg.T;
+    r.bg = background;
+    r.splat = at<float4>(gb, g.off[GEOM_SPLAT]);
+    r.final_Ts = at<float>(ib, im.off[IMG_FINAL_T]);
+    r.n_contrib = at<uint32_t>(ib, im.off[IMG_N_CONTRIB]);
+    r.dL_dpixels = dL_dpix;
+    r.dL_invdepths = dL_invdepths;
+    r.grad_inst = at<float>(bb, b.off[BIN_GRAD_INST]);
+    r.slot = slots_from_rect(tg.gx, tg.gy) ? nullptr : at<uint32_t>(bb, b.off[BIN_SLOT]);  // (render_bwd derives them)
+    r.valid = at<uint32_t>(bb, b.off[BIN_VALID]);
+    r.hit = at<uint8_t>(bb, b.off[BIN_HIT]);
+    r.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
+    r.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
+    return r;
+}
+
+// BACKWARD::render of one view (rasterizer_impl.cu:399-418; P, R > 0): the backward's tile order
+// (longest n_contrib first), then the per-(tile, Gaussian) gradient records
+static int backward_render_impl(int P, int R, const float* background, int width, int height, char* gb, char* bb,
+                                char* ib, const float* dL_dpix, const float* dL_invdepths, bool debug, hipStream_t s)
+{
+    const ImageLayout im = image_layout(width, height);
+    const RenderBwdArgs r = render_bwd_args(P, R, background, width, height, gb, bb, ib, dL_dpix, dL_invdepths);
+    {
+        ProfScope ps_(PK_TILE_ORDER, s);
+        HIP_TRY(launch_tile_order(nullptr, r.tile_work, r.T, at<uint32_t>(ib, im.off[IMG_TILE_ORDER]), s));
+    }
+    {
+        ProfScope ps_(PK_RENDER_BWD, s);  // valid[] was cleared by the forward's tile sort
+        HIP_TRY(launch_render_bwd(r, r.T, s));
+    }
+    DEBUG_SYNC(s);
+    return GSR_OK;
+}
+
+// What the single-view and the batched preprocess_bwd share: the argument checks, the per-Gaussian
+// parameters and the gradient outputs (the single view's extras -- radii, dL_dconic, dL_dinvdepth --
+// stay null here).
+static int preprocess_bwd_shared(PreprocessBwdArgs& p, int P, int D, int M, int width, int height,
+                                 const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                                 const float* opacities, const float* scales, float scale_modifier,
+                                 const float* rotations, const float* cov3D_precomp, bool has_invdepth,
+                                 bool antialiasing, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D,
+                                 float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                 unsigned accumulate)
+{
+    if (accumulate & ~(unsigned)GSR_ACC_ALL) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
+    if (dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
+    if (dc && colors_precomp)
+        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
+    if (dc && M > 0 && (!shs || !dL_dsh)) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
+    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
+    p.means3D = means3D; p.radii = nullptr; p.shs = shs; p.dc = dc; p.dL_ddc = dc ? dL_ddc : nullptr;
+    p.opacities = opacities; p.scales = scales; p.rotations = rotations; p.scale_modifier = scale_modifier;
+    p.cov3D_precomp = cov3D_precomp;
+    p.antialiasing = antialiasing;
+    p.has_invdepth = has_invdepth;
+    p.W = width; p.H = height;
+    p.dL_dconic = nullptr; p.dL_dinvdepth = nullptr;
+    p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
+    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (shs && M > 0) ? dL_dsh : nullptr;
+    p.dL_dscale = dL_dscale; p.dL_drot = dL_drot;
+    p.acc = accumulate;
+    return GSR_OK;
+}
+
+// One view's part of preprocess_bwd's arguments (L: its num_rendered; bb may be null when L == 0)
+static BwdView bwd_view(char* gb, char* bb, int P, int L, int width, int height, const float* viewmatrix,
+                        const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                        float* dL_dmean2D)
+{
+    const GeomLayout g = geom_layout(P);
+    const BinLayout b = bin_layout(L);
+    BwdView bv;
+    bv.view = viewmatrix; bv.proj = projmatrix; bv.campos = campos;
+    bv.focal_y = height / (2.0f * tan_fovy);
+    bv.focal_x = width / (2.0f * tan_fovx);
+    bv.tan_fovx = tan_fovx; bv.tan_fovy = tan_fovy;
+    bv.radii = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
+    bv.conic_opacity = at<float4>(gb, g.off[GEOM_CONIC_OPACITY]);
+    bv.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
+    bv.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
+    bv.tiles_touched = at<uint32_t>(gb, g.off[GEOM_TILES_TOUCHED]);
+    bv.grad_inst = L > 0 ? at<float>(bb, b.off[BIN_GRAD_INST]) : nullptr;
+    bv.valid = L > 0 ? at<uint32_t>(bb, b.off[BIN_VALID]) : nullptr;
+    bv.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
+    bv.dL_dmean2D = dL_dmean2D;
+    return bv;
 }
 
 int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int width, int height,
@@ -1064,94 +1170,33 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
                         float* dL_dscale, float* dL_drot, bool antialiasing, bool debug, unsigned accumulate,
                         gsr_stream_t stream)
 {
-    if (accumulate & ~(unsigned)GSR_ACC_ALL) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
-    if (dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
-    if (dc && colors_precomp)
-        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M > 0 && (!shs || !dL_dsh)) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
-    (void)colors_precomp;
+    PreprocessBwdViewsArgs A;
+    int rc = preprocess_bwd_shared(A.a, P, D, M, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
+                                   scale_modifier, rotations, cov3D_precomp, dL_invdepths != nullptr, antialiasing,
+                                   dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                                   accumulate);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return GSR_OK;
-    const GeomLayout g = geom_layout(P);
-    const ImageLayout im = image_layout(width, height);
-    const BinLayout b = bin_layout(R);
-    char* gb = geom_buffer;
-    char* ib = image_buffer;
-    char* bb = binning_buffer;
-    if (R > 0 && !bb) return fail(GSR_ERR_ALLOC, "null binning buffer");
-    const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    const uint32_t gy = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    const int T = (int)(gx * gy);
-    const int* rad = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
+    if (R > 0 && !binning_buffer) return fail(GSR_ERR_ALLOC, "null binning buffer");
     if ((dL_invdepths == nullptr) != (dL_dinvdepth == nullptr) && dL_dinvdepth == nullptr)
         return fail(GSR_ERR_INVALID, "dL_dinvdepth must be given with dL_invdepths");
-
-    // BACKWARD::render (rasterizer_impl.cu:399-418): per-(tile, Gaussian) gradient records
-    RenderBwdArgs r;
-    r.ranges = at<uint2>(ib, im.off[IMG_RANGES]);
-    r.tile_order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
-    r.tile_work = at<uint32_t>(ib, im.off[IMG_TILE_WORK]);
-    r.point_list = R > 0 ? at<uint32_t>(bb, b.off[BIN_POINT_LIST]) : nullptr;
-    r.W = width; r.H = height; r.grid_x = gx;
-    r.T = (int)(gx * gy);
-    r.bg = background;
-    r.splat = at<float4>(gb, g.off[GEOM_SPLAT]);
-    r.final_Ts = at<float>(ib, im.off[IMG_FINAL_T]);
-    r.n_contrib = at<uint32_t>(ib, im.off[IMG_N_CONTRIB]);
-    r.dL_dpixels = dL_dpix;
-    r.dL_invdepths = dL_invdepths;
-    r.grad_inst = R > 0 ? at<float>(bb, b.off[BIN_GRAD_INST]) : nullptr;
-    r.slot = R > 0 && !slots_from_rect(gx, gy) ? at<uint32_t>(bb, b.off[BIN_SLOT]) : nullptr;
-    r.valid = R > 0 ? at<uint32_t>(bb, b.off[BIN_VALID]) : nullptr;
-    r.hit = R > 0 ? at<uint8_t>(bb, b.off[BIN_HIT]) : nullptr;
-    r.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
-    r.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
-    if (R > 0) {
-        {
-            ProfScope ps_(PK_TILE_ORDER, s);
-            HIP_TRY(launch_tile_order(nullptr, at<uint32_t>(ib, im.off[IMG_TILE_WORK]), T,
-                                      at<uint32_t>(ib, im.off[IMG_TILE_ORDER]), s));
-        }
-        {
-            ProfScope ps_(PK_RENDER_BWD, s);  // valid[] was cleared by the forward's tile sort
-            HIP_TRY(launch_render_bwd(r, T, s));
-        }
-        DEBUG_SYNC(s);
+    if (R > 0) {  // (no instances: no records to write)
+        rc = backward_render_impl(P, R, background, width, height, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                  dL_invdepths, debug, s);
+        if (rc) return rc;
     }
-
     // BACKWARD::preprocess (rasterizer_impl.cu:423-449), with the per-Gaussian gather of the records:
-    // the batched kernel at one lane per Gaussian (launch_preprocess_bwd_single)
-    PreprocessBwdViewsArgs A;
-    PreprocessBwdArgs& p = A.a;
-    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
-    p.means3D = means3D; p.radii = rad; p.shs = shs; p.dc = dc; p.dL_ddc = dc ? dL_ddc : nullptr;
-    p.opacities = opacities; p.scales = scales; p.rotations = rotations; p.scale_modifier = scale_modifier;
-    p.cov3D_precomp = cov3D_precomp;
-    p.antialiasing = antialiasing;
-    p.has_invdepth = dL_invdepths != nullptr;
-    p.W = width; p.H = height;
-    p.dL_dconic = dL_dconic; p.dL_dinvdepth = dL_dinvdepth;
-    p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (shs && M > 0) ? dL_dsh : nullptr;
-    p.dL_dscale = dL_dscale; p.dL_drot = dL_drot;
-    p.acc = accumulate;
+    // the batched kernel at one lane per Gaussian (launch_preprocess_bwd_single), which also writes the
+    // reference glue's other render-pass gradients
     A.V = 1;
     A.g_begin = 0;
     A.g_end = P;
-    BwdView& bv = A.v[0];
-    bv.view = viewmatrix; bv.proj = projmatrix; bv.campos = campos;
-    bv.focal_y = height / (2.0f * tan_fovy);
-    bv.focal_x = width / (2.0f * tan_fovx);
-    bv.tan_fovx = tan_fovx; bv.tan_fovy = tan_fovy;
-    bv.radii = rad;
-    bv.conic_opacity = at<float4>(gb, g.off[GEOM_CONIC_OPACITY]);
-    bv.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
-    bv.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
-    bv.tiles_touched = at<uint32_t>(gb, g.off[GEOM_TILES_TOUCHED]);
-    bv.grad_inst = R > 0 ? at<float>(bb, b.off[BIN_GRAD_INST]) : nullptr;
-    bv.valid = R > 0 ? at<uint32_t>(bb, b.off[BIN_VALID]) : nullptr;
-    bv.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
-    bv.dL_dmean2D = dL_dmean2D;
+    A.v[0] = bwd_view(geom_buffer, binning_buffer, P, R, width, height, viewmatrix, projmatrix, campos, tan_fovx,
+                      tan_fovy, radii, dL_dmean2D);
+    A.a.radii = A.v[0].radii;
+    A.a.dL_dconic = dL_dconic;
+    A.a.dL_dinvdepth = dL_dinvdepth;
     {
         ProfScope ps_(PK_PREPROCESS_BWD, s);
         HIP_TRY(launch_preprocess_bwd_single(A, s));
@@ -1177,37 +1222,6 @@ int gsr_backward_dc(int P, int D, int M, int R, const float* background, int wid
                                dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot, antialiasing, debug, 0u, stream);
 }
 
-// render_bwd's arguments for one view (P, R > 0)
-static RenderBwdArgs render_bwd_args(int P, int R, const float* background, int width, int height, char* gb,
-                                     char* bb, char* ib, const float* dL_dpix, const float* dL_invdepths)
-{
-    const GeomLayout g = geom_layout(P);
-    const ImageLayout im = image_layout(width, height);
-    const BinLayout b = bin_layout(R);
-    const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    const uint32_t gy = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
-    RenderBwdArgs r;
-    r.ranges = at<uint2>(ib, im.off[IMG_RANGES]);
-    r.tile_order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
-    r.tile_work = at<uint32_t>(ib, im.off[IMG_TILE_WORK]);
-    r.point_list = at<uint32_t>(bb, b.off[BIN_POINT_LIST]);
-    r.W = width; r.H = height; r.grid_x = gx;
-    r.T = (int)(gx * gy);
-    r.bg = background;
-    r.splat = at<float4>(gb, g.off[GEOM_SPLAT]);
-    r.final_Ts = at<float>(ib, im.off[IMG_FINAL_T]);
-    r.n_contrib = at<uint32_t>(ib, im.off[IMG_N_CONTRIB]);
-    r.dL_dpixels = dL_dpix;
-    r.dL_invdepths = dL_invdepths;
-    r.grad_inst = at<float>(bb, b.off[BIN_GRAD_INST]);
-    r.slot = slots_from_rect(gx, gy) ? nullptr : at<uint32_t>(bb, b.off[BIN_SLOT]);  // (render_bwd derives them)
-    r.valid = at<uint32_t>(bb, b.off[BIN_VALID]);
-    r.hit = at<uint8_t>(bb, b.off[BIN_HIT]);
-    r.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
-    r.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
-    return r;
-}
-
 int gsr_backward_render(int P, int R, const float* background, int width, int height, char* geom_buffer,
                         char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_invdepths,
                         bool debug, gsr_stream_t stream)
@@ -1217,20 +1231,8 @@ int gsr_backward_render(int P, int R, const float* background, int width, int he
     if (P == 0 || R == 0) return GSR_OK;
     if (!geom_buffer || !image_buffer || !binning_buffer) return fail(GSR_ERR_ALLOC, "null state buffer");
     if (!dL_dpix) return fail(GSR_ERR_INVALID, "null dL_dpix");
-    const ImageLayout im = image_layout(width, height);
-    const RenderBwdArgs r = render_bwd_args(P, R, background, width, height, geom_buffer, binning_buffer, image_buffer,
-                                            dL_dpix, dL_invdepths);
-    {
-        ProfScope ps_(PK_TILE_ORDER, s);
-        HIP_TRY(launch_tile_order(nullptr, at<uint32_t>(image_buffer, im.off[IMG_TILE_WORK]), r.T,
-                                  at<uint32_t>(image_buffer, im.off[IMG_TILE_ORDER]), s));
-    }
-    {
-        ProfScope ps_(PK_RENDER_BWD, s);  // valid[] was cleared by the forward's tile sort
-        HIP_TRY(launch_render_bwd(r, r.T, s));
-    }
-    DEBUG_SYNC(s);
-    return GSR_OK;
+    return backward_render_impl(P, R, background, width, height, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                                dL_invdepths, debug, s);
 }
 
 int gsr_backward_preprocess_views(int V, int P, int D, int M, const int* R, int width, int height,
@@ -1268,61 +1270,27 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
 {
     if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
     if (g_begin < 0 || g_end > P || g_begin > g_end) return fail(GSR_ERR_INVALID, "range outside [0, P)");
-    if (accumulate & ~(unsigned)GSR_ACC_ALL) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
-    if (dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
-    if (dc && colors_precomp)
-        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M > 0 && (!shs || !dL_dsh)) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
+    PreprocessBwdViewsArgs A;
+    // a view rendered without an inverse-depth gradient has zero invdepth fields in its records:
+    // subtracting their (zero) term leaves its gradients bit-identical
+    const int rc = preprocess_bwd_shared(A.a, P, D, M, width, height, means3D, dc, shs, colors_precomp, opacities,
+                                         scales, scale_modifier, rotations, cov3D_precomp, has_invdepth, antialiasing,
+                                         dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale,
+                                         dL_drot, accumulate);
+    if (rc) return rc;
     if (!R || !viewmatrices || !projmatrices || !campos || !tan_fovx || !tan_fovy || !geom_buffers ||
         !binning_buffers || !dL_dmean2D)
         return fail(GSR_ERR_INVALID, "null per-view array");
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return GSR_OK;
-    const GeomLayout g = geom_layout(P);
-
-    PreprocessBwdViewsArgs A;
-    PreprocessBwdArgs& p = A.a;
-    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
-    p.means3D = means3D; p.radii = nullptr; p.shs = shs; p.dc = dc; p.dL_ddc = dc ? dL_ddc : nullptr;
-    p.opacities = opacities; p.scales = scales; p.rotations = rotations; p.scale_modifier = scale_modifier;
-    p.cov3D_precomp = cov3D_precomp;
-    p.antialiasing = antialiasing;
-    // a view rendered without an inverse-depth gradient has zero invdepth fields in its records:
-    // subtracting their (zero) term leaves its gradients bit-identical
-    p.has_invdepth = has_invdepth;
-    p.W = width; p.H = height;
-    p.dL_dconic = nullptr; p.dL_dinvdepth = nullptr;
-    p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (shs && M > 0) ? dL_dsh : nullptr;
-    p.dL_dscale = dL_dscale; p.dL_drot = dL_drot;
-    p.acc = accumulate;
     A.V = V;
     A.g_begin = g_begin;
     A.g_end = g_end;
     for (int v = 0; v < V; v++) {
-        char* gb = geom_buffers[v];
-        char* bb = binning_buffers[v];
-        const int L = R[v];
-        if (!gb || (L > 0 && !bb)) return fail(GSR_ERR_ALLOC, "null state buffer");
+        if (!geom_buffers[v] || (R[v] > 0 && !binning_buffers[v])) return fail(GSR_ERR_ALLOC, "null state buffer");
         if (!dL_dmean2D[v]) return fail(GSR_ERR_INVALID, "null per-view gradient");
-        const BinLayout b = bin_layout(L);
-        BwdView& bv = A.v[v];
-        bv.view = viewmatrices[v];
-        bv.proj = projmatrices[v];
-        bv.campos = campos[v];
-        bv.tan_fovx = tan_fovx[v];
-        bv.tan_fovy = tan_fovy[v];
-        bv.focal_y = height / (2.0f * tan_fovy[v]);
-        bv.focal_x = width / (2.0f * tan_fovx[v]);
-        bv.radii = (radii && radii[v]) ? radii[v] : at<int>(gb, g.off[GEOM_RADII]);
-        bv.conic_opacity = at<float4>(gb, g.off[GEOM_CONIC_OPACITY]);
-        bv.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
-        bv.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
-        bv.tiles_touched = at<uint32_t>(gb, g.off[GEOM_TILES_TOUCHED]);
-        bv.grad_inst = L > 0 ? at<float>(bb, b.off[BIN_GRAD_INST]) : nullptr;
-        bv.valid = L > 0 ? at<uint32_t>(bb, b.off[BIN_VALID]) : nullptr;
-        bv.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
-        bv.dL_dmean2D = dL_dmean2D[v];
+        A.v[v] = bwd_view(geom_buffers[v], binning_buffers[v], P, R[v], width, height, viewmatrices[v], projmatrices[v],
+                          campos[v], tan_fovx[v], tan_fovy[v], radii ? radii[v] : nullptr, dL_dmean2D[v]);
     }
     // BACKWARD::preprocess (rasterizer_impl.cu:423-449) of the whole batch: one pass over the Gaussians
     {
@@ -1347,7 +1315,7 @@ int gsr_backward_render_views(int V, int P, const int* R, const float* backgroun
     OrderJob oj[MAX_VIEWS];
     int no = 0;
     const ImageLayout im = image_layout(width, height);
-    const int T = (int)(((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X) * ((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y));
+    const int T = TileGrid(width, height).T;
     for (int v = 0; v < V; v++) {
         if (!image_buffers[v]) return fail(GSR_ERR_ALLOC, "null state buffer");
         if (R[v] > 0)
@@ -1550,12 +1518,11 @@ int gsr_debug_sorted_keys(const char* geometry_buffer, const char* binning_buffe
     const GeomLayout g = geom_layout(P);
     const BinLayout b = bin_layout(num_rendered);
     const ImageLayout im = image_layout(width, height);
-    const uint32_t gx = (uint32_t)((width + GSR_BLOCK_X - 1) / GSR_BLOCK_X);
-    const uint32_t gy = (uint32_t)((height + GSR_BLOCK_Y - 1) / GSR_BLOCK_Y);
+    const TileGrid tg(width, height);
     if (num_rendered > 0) {
         const uint32_t* point_list = at<uint32_t>(binning_buffer, b.off[BIN_POINT_LIST]);
-        if (keys_out && use_tile_diff(gx, gy))  // no tile ids were written: each tile's range carries its id
-            HIP_TRY(launch_debug_keys_from_ranges((int)(gx * gy), at<uint2>(image_buffer, im.off[IMG_RANGES]),
+        if (keys_out && use_tile_diff(tg.gx, tg.gy))  // no tile ids were written: each tile's range carries its id
+            HIP_TRY(launch_debug_keys_from_ranges(tg.T, at<uint2>(image_buffer, im.off[IMG_RANGES]),
                                                   point_list, at<uint32_t>(geometry_buffer, g.off[GEOM_DKEY]),
                                                   keys_out, s));
         else if (keys_out)
@@ -1565,7 +1532,7 @@ int gsr_debug_sorted_keys(const char* geometry_buffer, const char* binning_buffe
             HIP_TRY(hipMemcpyAsync(vals_out, point_list, 4 * (size_t)num_rendered, hipMemcpyDeviceToDevice, s));
     }
     if (ranges_out)
-        HIP_TRY(hipMemcpyAsync(ranges_out, image_buffer + im.off[IMG_RANGES], 8 * (size_t)gx * gy,
+        HIP_TRY(hipMemcpyAsync(ranges_out, image_buffer + im.off[IMG_RANGES], 8 * (size_t)tg.T,
                                hipMemcpyDeviceToDevice, s));
     return GSR_OK;
 }
@@ -1581,7 +1548,7 @@ int gsr_debug_set_depth_wide(int on)
 size_t gsr_debug_depth_sort_workspace_size(int n)
 {
     const size_t q = align_up(4 * (size_t)(n > 0 ? n : 0), 256);
-    return 4 * q + align_up(radix_status_bytes(n, 4), 256);
+    return 4 * q + align_up(radix_status_bytes(n), 256);
 }
 
 int gsr_debug_depth_sort(const uint32_t* keys, int n, uint32_t* out_ids, char* workspace, gsr_stream_t stream)

@@ -201,10 +201,10 @@ enum ImageArray {
 enum BinArray {
     BIN_POINT_LIST = 0,   // u32[L] Gaussian id of sorted position
     BIN_SORTED_TILES,     // u32[L] tile id of sorted position
-    BIN_SLOT,             // u32[L] gradient-record slot of sorted position (GSR_SLOT_LOCAL: minus the
-                          // Gaussian's emit_start, i.e. the instance's index in its rect)
-    BIN_GRAD_INST,        // f32x12[L] per-(tile, Gaussian) gradient records (backward); during the forward
-                          // it hosts the tile sort's ping-pong buffers (24 B/instance)
+    BIN_SLOT,             // u32[L] the sorted position's instance index inside its Gaussian's tile rect: its
+                          // gradient-record slot minus the Gaussian's emit_start (unused with slots_from_rect)
+    BIN_GRAD_INST,        // f32x10[L] per-(tile, Gaussian) gradient records (GRAD_REC; backward); during the
+                          // forward it hosts the tile sort's ping-pong buffers (24 B/instance)
     BIN_RADIX_SCRATCH,    // count matrix + digit totals of the tile sort
     BIN_VALID,            // u32[ceil(L/32)] bit per record slot: its gradient record was written (backward)
     BIN_HIT,              // u8[L] per sorted position: quadrants (bit w = 8x8 quadrant w) with a pixel the
@@ -234,29 +234,9 @@ __host__ __device__ inline uint2 rect_unpack(uint32_t r)
 // difference array fits a workgroup's LDS and whose tiles one tile-order pass covers (<= 8,192:
 // 1080p and below).
 constexpr int TILE_DIFF_MAX_CELLS = 8704;
-#ifndef GSR_TILE_DIFF
-#define GSR_TILE_DIFF 1
-#endif
-// records found through each Gaussian's record mask (GEOM_REC_MASK, set by render_bwd) instead of
-// the valid words
-#ifndef GSR_REC_MASK
-#define GSR_REC_MASK 1
-#endif
-// the tile sort's second digit carried in the id word (radix.hip tile_sort_fused_batch)
-#ifndef GSR_TILE_PACK
-#define GSR_TILE_PACK 1
-#endif
-// BIN_SLOT holds each instance's index inside its Gaussian's tile rect (its record slot minus the
-// Gaussian's emit_start) instead of the absolute record slot
-// floats per per-instance gradient record (GRAD_INST): 10 used; 10 = 40 B packed (8-B accesses), 12 =
-// 48 B (16-B accesses).  The tile sort's ping-pong buffers (<= 32 B per instance) live in the region.
-#ifndef GSR_GRAD_REC
-#define GSR_GRAD_REC 10
-#endif
-static_assert(GSR_GRAD_REC == 10 || GSR_GRAD_REC == 12, "gradient record: 10 or 12 floats");
-#ifndef GSR_SLOT_LOCAL
-#define GSR_SLOT_LOCAL 1
-#endif
+// floats per per-instance gradient record (BIN_GRAD_INST, GradField): 40 B packed (8-B accesses).  The
+// tile sort's ping-pong buffers (<= 32 B per instance) live in the region.
+constexpr int GRAD_REC = 10;
 // TEST-ONLY build (make refalpha -> refalpha/libgsr_hip_refalpha.so, never loaded by the package):
 // the render record carries the plain conic and the render kernels compute power and alpha in the
 // reference's operation order with the shared exp of gsr_ref_exp.h (forward.cu:353-363,
@@ -268,13 +248,7 @@ static_assert(GSR_GRAD_REC == 10 || GSR_GRAD_REC == 12, "gradient record: 10 or 
 // on grids of packed rects (rect_packable): no record slots at all -- render_bwd derives an instance's
 // index in its Gaussian's rect from the packed rect preprocess stores in the render record's free word
 // (SPLAT word 3) and the tile, and the tile sort moves 4 B per instance instead of 8
-#ifndef GSR_SLOT_RECT
-#define GSR_SLOT_RECT 1
-#endif
-__host__ __device__ inline bool slots_from_rect(uint32_t grid_x, uint32_t grid_y)
-{
-    return GSR_SLOT_LOCAL && GSR_SLOT_RECT && rect_packable(grid_x, grid_y);
-}
+__host__ __device__ inline bool slots_from_rect(uint32_t grid_x, uint32_t grid_y) { return rect_packable(grid_x, grid_y); }
 // the instance of tile (tx, ty) in the packed rect r: its index in the rect's y-major order
 // (duplicateWithKeys, rasterizer_impl.cu:98-109)
 __host__ __device__ inline uint32_t rect_local(uint32_t r, uint32_t tx, uint32_t ty)
@@ -284,7 +258,7 @@ __host__ __device__ inline uint32_t rect_local(uint32_t r, uint32_t tx, uint32_t
 }
 __host__ __device__ inline bool use_tile_diff(uint32_t grid_x, uint32_t grid_y)
 {
-    return GSR_TILE_DIFF && rect_packable(grid_x, grid_y) && (grid_x + 1) * (grid_y + 1) <= (uint32_t)TILE_DIFF_MAX_CELLS &&
+    return rect_packable(grid_x, grid_y) && (grid_x + 1) * (grid_y + 1) <= (uint32_t)TILE_DIFF_MAX_CELLS &&
            grid_x * grid_y <= 8192u;
 }
 
@@ -292,7 +266,7 @@ struct GeomLayout { size_t off[GEOM_COUNT + 1]; };
 struct ImageLayout { size_t off[IMG_COUNT + 1]; };
 struct BinLayout { size_t off[BIN_COUNT + 1]; };
 
-size_t radix_status_bytes(int n, int npass);
+size_t radix_status_bytes(int n);
 size_t fused_pass1_scratch_bytes(int P);  // radix.hip: the fused emission pass's count matrix
 
 inline GeomLayout geom_layout(int P)
@@ -301,7 +275,7 @@ inline GeomLayout geom_layout(int P)
     size_t sizes[GEOM_COUNT] = {4 * p, 4 * p, p, 8 * p, 16 * p, 12 * p, 4 * p, 4 * p, 48 * p,
                                 4 * p, 4 * p, 4 * p, 8 * p, 8 * p,
                                 // (after the depth sort, the fused tile-sort pass's count matrix)
-                                std::max(24 * p + 2048, fused_pass1_scratch_bytes(P)), radix_status_bytes(P, 4),
+                                std::max(24 * p + 2048, fused_pass1_scratch_bytes(P)), radix_status_bytes(P),
                                 16 * ((p + SCAN_ITEMS - 1) / SCAN_ITEMS + 1), 4 * p};
     GeomLayout l;
     size_t o = 0;
@@ -326,7 +300,7 @@ inline ImageLayout image_layout(int W, int H)
 inline BinLayout bin_layout(int L)
 {
     size_t n = (size_t)(L > 0 ? L : 0);
-    size_t sizes[BIN_COUNT] = {4 * n, 4 * n, 4 * n, 4 * (size_t)GSR_GRAD_REC * n + 4096, radix_status_bytes(L, 4),
+    size_t sizes[BIN_COUNT] = {4 * n, 4 * n, 4 * n, 4 * (size_t)GRAD_REC * n + 4096, radix_status_bytes(L),
                                4 * ((n + 31) / 32), n};
     BinLayout l;
     size_t o = 0;

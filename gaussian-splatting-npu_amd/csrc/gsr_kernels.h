@@ -77,13 +77,13 @@ struct RenderBwdArgs {
     const float* dL_invdepths;  // (1,H,W) or null
     const uint32_t* slot;       // gradient-record slot of each sorted position
     uint32_t* valid;            // bit (slot & 31) of valid[slot >> 5] set for every record written (cleared by emit)
-    float* grad_inst;           // f32x12[L]: one gradient record per (tile, Gaussian) entry, at its record slot
+    float* grad_inst;           // f32x10[L]: one gradient record per (tile, Gaussian) entry, at its record slot
     const uint8_t* hit;         // BIN_HIT (render_fwd): the quadrants each entry contributed to
     const uint32_t* emit_start; // GEOM_EMIT_START: first record slot of each Gaussian
     uint32_t* rec_mask;         // GEOM_REC_MASK: bit (slot - emit_start[id]) set for records at local index < 32
 };
 
-// Layout of one per-instance gradient record (GRAD_REC floats: 40 B, or 48 B padded).  With u = G dL/dalpha
+// Layout of one per-instance gradient record (GRAD_REC floats: 40 B packed).  With u = G dL/dalpha
 // per pixel, the mean2D fields hold Sx = sum u dx, Sy = sum u dy and the conic fields
 // sum u dx^2, u dx dy, u dy^2 -- WITHOUT the per-Gaussian factors (backward.cu:619-636):
 // preprocess_bwd forms dL/dmean2D = (a Sx + b Sy, b Sx + c Sy) * (-opacity W/2, -opacity H/2)
@@ -92,10 +92,6 @@ enum GradField {
     GF_MEAN2D_X = 0, GF_MEAN2D_Y, GF_CONIC_A, GF_CONIC_B, GF_CONIC_C, GF_OPACITY, GF_COLOR_R, GF_COLOR_G,
     GF_COLOR_B, GF_INVDEPTH, GF_NUM
 };
-#ifndef GSR_GRAD_REC
-#define GSR_GRAD_REC 10  // (the same default as gsr_common.h, which sizes BIN_GRAD_INST with it)
-#endif
-constexpr int GRAD_REC = GSR_GRAD_REC;
 
 // In-place gradient accumulation (gsr_backward_dc_acc): bit set = that output array is added to.
 enum AccBits : uint32_t {
@@ -263,7 +259,6 @@ struct TileSortJob {
     const uint32_t* sorted_ids;
     const uint32_t* offsets;      // inclusive scan of the tile counts in depth order
     const uint2* sorted_rects;
-    const uint32_t* rec_start;    // first gradient-record slot per Gaussian
     char* pass1_scratch;          // fused_pass1_scratch_bytes(P): the first pass's count matrix
     uint32_t *k0, *v0, *k1, *v1;  // ping-pong (v: u32x2)
     char* scratch;                // radix_status_bytes(L) for the later passes

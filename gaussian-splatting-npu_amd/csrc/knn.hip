@@ -216,7 +216,7 @@ KnnLayout knn_layout(int P)
 size_t knn_workspace_bytes(int P)
 {
     const KnnLayout l = knn_layout(P);
-    return l.off[9] + align_up(radix_status_bytes(P, 4), 256) + 32 * KNN_BOUNDS_BLOCKS;
+    return l.off[9] + align_up(radix_status_bytes(P), 256) + 32 * KNN_BOUNDS_BLOCKS;
 }
 
 // Host: bounds -> grid of ~P/2 cells (at most 2P + 64), then sort, gather, query.
@@ -225,7 +225,7 @@ hipError_t knn_dist2(int P, const float* pts, float* dist2, char* ws, uint32_t* 
     if (P <= 0) return hipSuccess;
     const KnnLayout l = knn_layout(P);
     auto at32 = [&](int i) { return reinterpret_cast<uint32_t*>(ws + l.off[i]); };
-    float* partial = reinterpret_cast<float*>(ws + l.off[9] + align_up(radix_status_bytes(P, 4), 256));
+    float* partial = reinterpret_cast<float*>(ws + l.off[9] + align_up(radix_status_bytes(P), 256));
     uint32_t* bounds_dev = nullptr;
     hipError_t e;
     if ((e = hipHostGetDevicePointer((void**)&bounds_dev, host_bounds, 0)) != hipSuccess) return e;

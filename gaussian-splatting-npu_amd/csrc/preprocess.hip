@@ -236,8 +236,8 @@ __device__ __forceinline__ void preprocess_one(const PreprocessArgs& a, int idx,
 // Gaussians (a batch of views, gsr_forward_views): their parameters and SH rows are read from HBM
 // once, each view's outputs go to its own buffers (A.a[v]).
 // Threads (Gaussians) per preprocess workgroup.  64 lets the next view's preprocess slip into
-// single-wave holes beside a running render_bwd, but once render_bwd frees 4-wave holes
-// (BWD_TPW) 256 measures as fast (same-box A/B 2,302 vs 2,325 Mpix/s).
+// single-wave holes beside a running render_bwd, but 256 measures as fast (same-box A/B 2,302 vs
+// 2,325 Mpix/s).
 constexpr int PF_TPB = 256;
 
 template <int NV>

@@ -49,20 +49,13 @@ __device__ __forceinline__ void rec_batch(const bool (&v)[B], const uint32_t (&s
 #pragma unroll
     for (int k = 0; k < B; k++) {
         if (v[k]) {
-            if constexpr (GRAD_REC % 4 == 0) {  // 16-B aligned records
-                const float4* rec = reinterpret_cast<const float4*>(grad_inst + (size_t)sl[k] * GRAD_REC);
-                const float4 a0 = rec[0], a1 = rec[1], a2 = rec[2];
-                r[k][0] = a0.x; r[k][1] = a0.y; r[k][2] = a0.z; r[k][3] = a0.w;
-                r[k][4] = a1.x; r[k][5] = a1.y; r[k][6] = a1.z; r[k][7] = a1.w;
-                r[k][8] = a2.x; r[k][9] = a2.y;
-            } else {  // packed 40-B records
-                const float2* rec = reinterpret_cast<const float2*>(grad_inst + (size_t)sl[k] * GRAD_REC);
+            // packed 40-B records: 8-B loads
+            const float2* rec = reinterpret_cast<const float2*>(grad_inst + (size_t)sl[k] * GRAD_REC);
 #pragma unroll
-                for (int h = 0; h < GF_NUM / 2; h++) {
-                    const float2 x = rec[h];
-                    r[k][2 * h] = x.x;
-                    r[k][2 * h + 1] = x.y;
-                }
+            for (int h = 0; h < GF_NUM / 2; h++) {
+                const float2 x = rec[h];
+                r[k][2 * h] = x.x;
+                r[k][2 * h + 1] = x.y;
             }
         }
     }
@@ -134,10 +127,6 @@ template <int B = REC_BATCH>
 __device__ __forceinline__ void gather_any(uint32_t e0, uint32_t n, uint32_t mask, const uint32_t* valid,
                                            const float* grad_inst, float (&g)[GF_NUM])
 {
-    if (!GSR_REC_MASK) {
-        gather_range<B>(e0, e0 + n, valid, grad_inst, g);
-        return;
-    }
     gather_mask<B>(e0, mask, grad_inst, g);
     if (n > 32u) gather_range<B, false>(e0 + 32u, e0 + n, valid, grad_inst, g);
 }
@@ -819,19 +808,14 @@ __global__ void __launch_bounds__(256) preprocess_bwd_views_kernel(const Preproc
 }
 
 // The same work as preprocess_bwd_views_kernel<LPG, true> for the interleaved SH layout, with
-// GSR_PBWD_PIPE chunks of G Gaussians per workgroup in straight-line code: every chunk's view
+// PBWD_CHUNKS chunks of G Gaussians per workgroup in straight-line code: every chunk's view
 // inputs (record range and mask) are loaded up front, so a later chunk's record gathers are issued
 // together with its parameter and SH loads -- one memory round trip before its compute instead of two.
 // (As a loop over chunks the compiler keeps ~60 more VGPRs live: 2 waves/SIMD instead of 4.)
-#ifndef GSR_PBWD_PIPE
-#define GSR_PBWD_PIPE 2  // chunks per workgroup, lane groups (the batch launches; 0: one chunk, the plain kernel)
-#endif
-#ifndef GSR_PBWD_PIPE1
-#define GSR_PBWD_PIPE1 0  // the same for the single view's one lane per Gaussian
-#endif
-#ifndef GSR_PBWD_PIPE2
-#define GSR_PBWD_PIPE2 0  // the same for two lanes per Gaussian (batches of 1-2 views)
-#endif
+// From four lanes per Gaussian up (batches of 3+ views).  One and two lanes (the single view, batches of
+// 1-2 views) keep the plain one-chunk kernel: the second chunk's registers cost the single view a wave
+// per SIMD (135 -> 140 us).
+constexpr int PBWD_CHUNKS = 2;
 template <int LPG>
 __device__ __forceinline__ void pbwd_chunk(const PreprocessBwdViewsArgs& A, float* s_sh, const float* cam, int chunk,
                                            const ViewIn& vi)
@@ -882,7 +866,7 @@ __device__ __forceinline__ void pbwd_chunk(const PreprocessBwdViewsArgs& A, floa
 }
 
 template <int LPG, int NCH>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LPG == 1 ? 3 : 1)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
 preprocess_bwd_views_pipe_kernel(const PreprocessBwdViewsArgs A, int nchunks)
 {
     constexpr int G = 256 / LPG;
@@ -915,12 +899,11 @@ static hipError_t launch_views(const PreprocessBwdViewsArgs& A, hipStream_t s)
 {
     constexpr int G = 256 / LPG;
     const dim3 grid((A.g_end - A.g_begin + G - 1) / G), block(256);
-    constexpr int NCH = LPG >= 4 ? GSR_PBWD_PIPE : LPG == 2 ? GSR_PBWD_PIPE2 : GSR_PBWD_PIPE1;
-    if constexpr (NCH > 0) {
+    if constexpr (LPG >= 4) {
         if (staged_layout(A.a) && !A.a.dc) {
-            const int nchunks = (int)grid.x, blocks = (nchunks + NCH - 1) / NCH;
-            hipLaunchKernelGGL((preprocess_bwd_views_pipe_kernel<LPG, NCH>), dim3(blocks), block, staged_lds_bytes(G), s,
-                               A, nchunks);
+            const int nchunks = (int)grid.x, blocks = (nchunks + PBWD_CHUNKS - 1) / PBWD_CHUNKS;
+            hipLaunchKernelGGL((preprocess_bwd_views_pipe_kernel<LPG, PBWD_CHUNKS>), dim3(blocks), block,
+                               staged_lds_bytes(G), s, A, nchunks);
             return hipGetLastError();
         }
     }

@@ -3,8 +3,9 @@
 // binning built on it.
 //
 // Binning scheme (same result as the reference's 64-bit tile|depth key sort):
-//   1. sort the P Gaussians by depth bits (4 x 8-bit passes; ties keep index order;
-//      culled Gaussians carry key 0xFFFFFFFF and land last);
+//   1. sort the P Gaussians by depth bits (three 9-bit passes, the third relative to the smallest
+//      key -- see DEPTH3 -- or four 8-bit passes when the keys' range is too wide for that; ties keep
+//      index order; culled Gaussians carry key 0xFFFFFFFF and land last);
 //   2. the (tile, Gaussian) instances in that depth order (y-major, then x, inside each
 //      Gaussian's rect, exactly like duplicateWithKeys, rasterizer_impl.cu:98-109) are
 //      stably sorted by tile id alone: ceil(bit/8) passes over bit = msb(T) bits (2 at 1080p)
@@ -15,13 +16,15 @@
 // (tile << 32 | depth bits) is bit-identical to the reference's.
 //
 // One pass = three kernels, no inter-workgroup waiting: (1) every 2048-element chunk counts
-// its digits (digit-major count matrix); (2) one workgroup per digit scans that digit's row
-// over the chunks; (3) every chunk ranks its elements stably per digit (wave-level ballot
-// match + per-wave running counters in LDS), adds the digit's offset (exclusive scan of the
-// 2^bits digit totals, redone in LDS by each chunk) and its row prefix, and scatters through
-// LDS so that global writes are contiguous runs per digit.  Digit widths are balanced over
-// the passes (the tile sort at 1080p: 13 bits = 7 + 6).  The payload is one u32 (the
-// element's input index in pass 1).
+// its digits (count matrix, see cm_index); (2) each digit's counts are scanned over the chunks
+// (a row scan, or a column scan of the chunk-major matrix); (3) every chunk ranks its elements
+// stably per digit (wave-level ballot match + per-wave running counters in LDS), adds the
+// digit's offset (exclusive scan of the 2^bits digit totals, redone in LDS by each chunk) and
+// its row prefix, and scatters through LDS so that global writes are contiguous runs per
+// digit.  The three-pass depth sort has no kernel (2): its scatter derives the offsets from
+// chunk-group sums (GS_CHUNKS).  Digit widths are balanced over the passes (the tile sort at
+// 1080p: 13 bits = 6 + 7, see tile_sort_fused_batch).  The payload is one u32 (the element's
+// input index in pass 1).
 #include "gsr_common.h"
 #include "gsr_kernels.h"
 
@@ -31,20 +34,16 @@ namespace gsr {
 
 constexpr int RS_THREADS = 256;
 constexpr int RS_THREADS_WIDE = 512;            // 9-bit passes: 4,096-key chunks
-constexpr int RS_ITEMS = 8;                     // elements per thread, long sorts (the tile sort; 16: -20 % slower)
-constexpr int RS_ITEMS_SHORT = 8;               // short sorts (the depth sort; 4 measures the same)
-constexpr int RS_SHORT_MAX = 1 << 21;           // n up to which a sort counts as short
+constexpr int RS_ITEMS = 8;                     // elements per thread (16: -20 % slower on the tile sort; 4 measures
+                                                // the same on the depth sort)
 constexpr int RS_MAXBINS = 256;
 constexpr int RS_SCRATCH_BINS = 512;            // count-matrix rows reserved per sort (9-bit depth digits)
-// GSR_DEPTH_GSUM: the three-pass depth sort launches no column scan.  Each count workgroup also adds
-// its digit counts into its chunk group's row (GS_CHUNKS chunks per group, atomic adds of integers:
-// exact in any order), and each scatter workgroup derives its own digit offsets from the group rows
-// and the chunk rows of its group in its prologue (<= 31 loads per digit at P = 1M) -- 3 launches per
-// depth sort fewer (the single view's train.py path runs its depth sort alone on the GPU: each launch
-// is latency, ~7 us).  The pass-3 key range is reduced by workgroup 0 of the pass-2 count kernel.
-#ifndef GSR_DEPTH_GSUM
-#define GSR_DEPTH_GSUM 1
-#endif
+// The three-pass depth sort launches no scan kernel.  Each count workgroup also adds its digit counts
+// into its chunk group's row (GS_CHUNKS chunks per group, atomic adds of integers: exact in any
+// order), and each scatter workgroup derives its own digit offsets from the group rows and the chunk
+// rows of its group in its prologue (<= 31 loads per digit at P = 1M) -- 3 launches per depth sort
+// fewer (the single view's train.py path runs its depth sort alone on the GPU: each launch is
+// latency, ~7 us).  The pass-3 key range is reduced by workgroup 0 of the pass-2 count kernel.
 constexpr int GS_CHUNKS = 16;
 
 // Kernel-name tags: which sort a radix pass belongs to (the depth sort, the tile sort's later
@@ -61,9 +60,6 @@ __device__ __forceinline__ uint32_t digit_of(uint32_t k, int shift, uint32_t mas
 // over the chunks reads 16 digits = 64 B per chunk row -- for passes of at most CS_CHUNKS chunks, which
 // one LDS block of radix_colscan_kernel scans: the depth sort), or digit-major counts[d * nchunks + c]
 // (one row-scan workgroup per digit: the tile sort's thousands of chunks).
-#ifndef GSR_COLSCAN
-#define GSR_COLSCAN 1
-#endif
 __device__ __forceinline__ size_t cm_index(uint32_t d, uint32_t c, uint32_t nb, uint32_t nchunks, bool cmaj)
 {
     return cmaj ? (size_t)c * nb + d : (size_t)d * nchunks + c;
@@ -74,22 +70,19 @@ __device__ __forceinline__ size_t cm_index(uint32_t d, uint32_t c, uint32_t nb, 
 // of 8 (scatter_grid) the chunks [x q, (x + 1) q) of block class x = b % 8 run on one XCD, in order.
 // A digit's output runs from consecutive chunks are adjacent in memory: their partial cache lines
 // then meet in one L2 instead of being written back from several.  A bijection on [0, grid.x).
-#ifndef GSR_XCD_CHUNKS
-#define GSR_XCD_CHUNKS 1
-#endif
 __device__ __forceinline__ uint32_t xcd_chunk(uint32_t b, uint32_t gx)
 {
-    if (!GSR_XCD_CHUNKS || (gx & 7u)) return b;
+    if (gx & 7u) return b;
     return (b & 7u) * (gx >> 3) + (b >> 3);
 }
-static inline unsigned scatter_grid(int maxc) { return GSR_XCD_CHUNKS ? (unsigned)((maxc + 7) & ~7) : (unsigned)maxc; }
+static inline unsigned scatter_grid(int maxc) { return (unsigned)((maxc + 7) & ~7); }
 
 // The depth sort in three 9-bit passes: passes 1 and 2 take key bits [0, 9) and [9, 18); pass 3
 // takes bits [18, 32) RELATIVE to the smallest key that is not 0xFFFFFFFF (culled):
 // digit = (k >> 18) - (min >> 18), and 511 for 0xFFFFFFFF.  That is monotone in k, so the three passes
 // sort exactly whenever the keys other than 0xFFFFFFFF span at most 511 values of k >> 18 (visible
 // depths within a factor of ~2^16: 0.2 ... 13,000).  Pass 1 gathers the range (per-chunk min / max,
-// reduced by an extra workgroup of its scan into RangeWord).  A wider range is reported to the host
+// reduced by workgroup 0 of pass 2's count kernel into RangeWord).  A wider range is reported to the host
 // (SortJob::host_wide, a pinned word it reads with num_rendered): that call's depth sort then runs
 // again in four 8-bit passes (radix_sort_batch four_pass; capi.hip depth_sort_rerun_wide) -- per call,
 // no state is kept.
@@ -132,11 +125,11 @@ struct CountJob {
     uint32_t* cmin;            // non-null: per-chunk min / max of the keys other than 0xFFFFFFFF
     uint32_t* cmax;
     bool cmaj;                 // chunk-major count matrix (cm_index)
-    // GSR_DEPTH_GSUM: non-null: each chunk's digit counts are also added into
+    // non-null (the three-pass depth sort): each chunk's digit counts are also added into
     // gsum[(chunk / GS_CHUNKS) * nb + d] (zero on entry)
     uint32_t* gsum = nullptr;
     // non-null: workgroup 0 reduces the per-chunk key min / max of an earlier pass (rcmin / rcmax,
-    // rnchunks chunks) into *range_out (the relative pass's RangeWord; reduce_range)
+    // rnchunks chunks) into *range_out (the relative pass's RangeWord; reduce_range_nt)
     RangeWord* range_out = nullptr;
     const uint32_t* rcmin = nullptr;
     const uint32_t* rcmax = nullptr;
@@ -296,58 +289,12 @@ struct RowJob {
     uint32_t* counts;
     int nchunks;
     uint32_t* totals;
-    uint32_t* host_wide;       // (range_out) pinned host word: set to 1 when the range does not fit
-    // non-null (the depth sort's first pass): workgroup `nbins` (one past the digit rows) reduces the
-    // per-chunk min / max into *range_out for a relative pass on bits [rel_shift, rel_shift + rel_bits)
-    const uint32_t* cmin;
-    const uint32_t* cmax;
-    RangeWord* range_out;
-    int nbins, rel_shift, rel_bits;
+    int nbins;  // (the column scan: digits of the chunk-major matrix)
 };
-// the extra workgroup of a row scan: the keys' range from the per-chunk min / max (RowJob)
-__device__ void reduce_range(const RowJob& J)
-{
-    __shared__ uint32_t s_mm[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
-    for (int c = tid; c < J.nchunks; c += RS_THREADS) {
-        mn = min(mn, J.cmin[c]);
-        mx = max(mx, J.cmax[c]);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        mn = min(mn, (uint32_t)__shfl_xor((int)mn, off, 64));
-        mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
-    }
-    if (lane == 0) {
-        s_mm[0][w] = mn;
-        s_mm[1][w] = mx;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        mn = min(min(s_mm[0][0], s_mm[0][1]), min(s_mm[0][2], s_mm[0][3]));
-        mx = max(max(s_mm[1][0], s_mm[1][1]), max(s_mm[1][2], s_mm[1][3]));
-        RangeWord r;
-        if (mn > mx) {  // nothing but 0xFFFFFFFF
-            r.base = 0u;
-            r.fits = 1u;
-        } else {
-            r.base = mn >> J.rel_shift;
-            // the largest relative digit stays below 2^rel_bits - 1, the digit of 0xFFFFFFFF
-            r.fits = ((mx >> J.rel_shift) - r.base) <= (1u << J.rel_bits) - 2u ? 1u : 0u;
-        }
-        *J.range_out = r;
-        if (!r.fits && J.host_wide) __hip_atomic_store(J.host_wide, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
 template <typename KIND>
 __global__ void __launch_bounds__(RS_THREADS) radix_rowscan_kernel(const ViewBatch<RowJob> B)
 {
     const RowJob& J = B.v[blockIdx.y];
-    if (J.cmin && (int)blockIdx.x == J.nbins) {
-        reduce_range(J);
-        return;
-    }
     uint32_t* counts = J.counts;
     const int nchunks = J.nchunks;
     uint32_t* totals = J.totals;
@@ -387,10 +334,6 @@ template <typename KIND>
 __global__ void __launch_bounds__(RS_THREADS) radix_rowscan_lds_kernel(const ViewBatch<RowJob> RB)
 {
     const RowJob& J = RB.v[blockIdx.y];
-    if (J.cmin && (int)blockIdx.x == J.nbins) {
-        reduce_range(J);
-        return;
-    }
     uint32_t* counts = J.counts;
     const int nchunks = J.nchunks;
     uint32_t* totals = J.totals;
@@ -437,12 +380,11 @@ __global__ void __launch_bounds__(RS_THREADS) radix_rowscan_lds_kernel(const Vie
     for (int c = tid; c < nchunks; c += RS_THREADS) row[c] = s_row[c];
 }
 
-// (2') GSR_COLSCAN: the exclusive scan over the chunks of each digit's counts, on the chunk-major
-// matrix: workgroup g takes digits [16 g, 16 g + 16); thread (dl = tid >> 4, sg = tid & 15) scans a
+// (2'') the exclusive scan over the chunks of each digit's counts, on the chunk-major matrix:
+// workgroup g takes digits [16 g, 16 g + 16); thread (dl = tid >> 4, sg = tid & 15) scans a
 // contiguous segment of chunks of digit 16 g + dl; blocks of CS_CHUNKS chunks are staged in LDS with
 // every load in flight (16 digits = 64 contiguous bytes per chunk row), each digit's running total
-// carried from block to block.  Workgroup ceil(nbins / 16) (the depth sort's first pass) reduces the
-// keys' range instead.
+// carried from block to block.
 constexpr int CS_DIG = 16;
 constexpr int CS_CHUNKS = 960;  // chunks per LDS block (960 x 17 words = 64 KB)
 template <typename KIND>
@@ -450,10 +392,6 @@ __global__ void __launch_bounds__(RS_THREADS) radix_colscan_kernel(const ViewBat
 {
     const RowJob& J = B.v[blockIdx.y];
     const int ngroups = (J.nbins + CS_DIG - 1) / CS_DIG;
-    if (J.cmin && (int)blockIdx.x == ngroups) {
-        reduce_range(J);
-        return;
-    }
     if ((int)blockIdx.x >= ngroups) return;
     __shared__ uint32_t s_col[CS_CHUNKS * (CS_DIG + 1)];  // [chunk][digit], rows padded to 17 words
     const int tid = threadIdx.x, dl = tid >> 4, sg = tid & 15;
@@ -535,7 +473,7 @@ struct SortPassArgs {
     int mode;                // DigitMode
     const RangeWord* range;
     bool cmaj;               // chunk-major count matrix (cm_index)
-    // GSR_DEPTH_GSUM: non-null: row_prefix holds the raw chunk-major counts (no column scan ran) and
+    // non-null (the three-pass depth sort): row_prefix holds the raw chunk-major counts (no scan ran) and
     // gsum their per-group sums; the digit offsets are derived from both here
     const uint32_t* gsum = nullptr;
 };
@@ -785,7 +723,7 @@ __global__ void __launch_bounds__(NT) radix_scatter_kernel(const ViewBatch<SortP
 // Emission fused into the first tile-sort pass.  Chunk c of a view = the instances of its depth
 // ranks [c * FE_RANKS, (c + 1) * FE_RANKS) in emission order (depth rank, then y-major inside the
 // rect: duplicateWithKeys, rasterizer_impl.cu:98-109).  Both kernels stage the chunk's ranks
-// (instance start, rect, and for the scatter the Gaussian id and record start) in LDS and derive
+// (instance start, rect, and for the scatter the Gaussian id) in LDS and derive
 // every instance -- owner by binary search over the starts, tile from the owner's rect -- instead of
 // reading emitted (tile, slot, id) arrays: the 12 B per instance that emission wrote and the pass
 // read back (twice: count and scatter) never touch HBM.  The scatter ranks a chunk in rounds of
@@ -793,16 +731,12 @@ __global__ void __launch_bounds__(NT) radix_scatter_kernel(const ViewBatch<SortP
 // running output position from round to round, so a chunk of any size stays stable.
 // ---------------------------------------------------------------------------
 constexpr int FE_RANKS = 256;
-#ifndef GSR_TILE_SOA
-#define GSR_TILE_SOA 1
-#endif
 
 struct FusedPassArgs {
     int P, L, nchunks;
     const uint32_t* sorted_ids;
     const uint32_t* offsets;
     const uint2* sorted_rects;
-    const uint32_t* rec_start;
     uint32_t* counts;  // (bins, nchunks)
     uint32_t* totals;  // (bins)
     // outputs: keys_out / vals_out (u32x2) -- or, if this is the only pass, the final arrays
@@ -821,21 +755,13 @@ struct FusedPassArgs {
     uint32_t* soa_y;
 };
 
-// GSR_FE_AOS: a rank's fields as one 16-B {start, x0 | y0 << 16, w, 1/w} and one 8-B {record start,
-// id} LDS entry (one ds_read_b128 + one ds_read_b64 per derived instance at the write-out, whose
-// owners are random across the lanes), instead of seven separate arrays (seven reads)
-#ifndef GSR_FE_AOS
-#define GSR_FE_AOS 1
-#endif
+// A rank's fields as one 16-B {start, x0 | y0 << 16, w, 1/w} LDS entry and its Gaussian id (one
+// ds_read_b128 + one ds_read_b32 per derived instance at the write-out, whose owners are random
+// across the lanes), not one array per field
 struct FeRanks {
     uint32_t start[FE_RANKS];  // (also in geo: the owner search reads this array)
-#if GSR_FE_AOS
     uint4 geo[FE_RANKS];
-    uint2 idr[FE_RANKS];
-#else
-    uint32_t x0[FE_RANKS], y0[FE_RANKS], w[FE_RANKS], g[FE_RANKS], rec[FE_RANKS];
-    float rw[FE_RANKS];  // 1 / w
-#endif
+    uint32_t id[FE_RANKS];
 };
 
 // Stages chunk c's ranks; [wbeg, wend) is its instance range.  Ends with a barrier.
@@ -844,35 +770,18 @@ __device__ __forceinline__ void fe_stage(const FusedPassArgs& J, int c, FeRanks&
 {
     const int tid = threadIdx.x;
     const int k0 = c * FE_RANKS, k = k0 + tid;
-    uint32_t start = 0xFFFFFFFFu, x0 = 0, y0 = 0, wd = 1, g = 0, rec = 0;
+    uint32_t start = 0xFFFFFFFFu, x0 = 0, y0 = 0, wd = 1, g = 0;
     if (k < J.P) {
         start = k == 0 ? 0u : J.offsets[k - 1];
         const uint2 rc = J.sorted_rects[k];
         x0 = rc.x & 0xFFFFu;
         y0 = rc.x >> 16;
         wd = max((rc.y & 0xFFFFu) - x0, 1u);
-        if (IDS) {
-            g = J.sorted_ids[k];
-            // GSR_SLOT_LOCAL: the instance's index inside its Gaussian's rect is stored instead of the
-            // absolute record slot (render_bwd adds emit_start[id], which it loads anyway): no
-            // dependent gather of the record start behind the id here
-            rec = GSR_SLOT_LOCAL ? 0u : J.rec_start[g];
-        }
+        if (IDS) g = J.sorted_ids[k];
     }
     s.start[tid] = start;
-#if GSR_FE_AOS
     s.geo[tid] = make_uint4(start, x0 | (y0 << 16), wd, __float_as_uint(1.0f / (float)wd));
-    if (IDS) s.idr[tid] = make_uint2(rec, g);
-#else
-    s.x0[tid] = x0;
-    s.y0[tid] = y0;
-    s.w[tid] = wd;
-    s.rw[tid] = 1.0f / (float)wd;
-    if (IDS) {
-        s.g[tid] = g;
-        s.rec[tid] = rec;
-    }
-#endif
+    if (IDS) s.id[tid] = g;
     wbeg = k0 == 0 ? 0u : J.offsets[k0 - 1];
     wend = J.offsets[min(k0 + FE_RANKS, J.P) - 1];
     __syncthreads();
@@ -891,14 +800,9 @@ __device__ __forceinline__ int fe_owner(const FeRanks& s, uint32_t sl)
 
 __device__ __forceinline__ uint32_t fe_tile(const FeRanks& s, int j, uint32_t sl, uint32_t gx, uint32_t& local)
 {
-#if GSR_FE_AOS
     const uint4 q = s.geo[j];
     const uint32_t st = q.x, x0 = q.y & 0xFFFFu, y0 = q.y >> 16, wj = q.z;
     const float rw = __uint_as_float(q.w);
-#else
-    const uint32_t st = s.start[j], x0 = s.x0[j], y0 = s.y0[j], wj = s.w[j];
-    const float rw = s.rw[j];
-#endif
     local = sl - st;
     // local / wj by a reciprocal estimate (off by at most one for local < 2^24) and one correction
     // each way, instead of the ~40-instruction integer division
@@ -1077,12 +981,9 @@ __global__ void __launch_bounds__(RS_THREADS) fused_pass1_scatter_kernel(const V
                 const uint32_t k = fe_tile(s, j, r0 + li, gx, local);
                 const uint32_t d = k & mask;
                 const uint32_t dst = s_base[d] + ((uint32_t)lpos - s_blk[d]);
-#if GSR_FE_AOS
-                const uint2 ig = s.idr[j];
-                const uint2 v = make_uint2(ig.x + local, ig.y);
-#else
-                const uint2 v = make_uint2(s.rec[j] + local, s.g[j]);
-#endif
+                // (slot, id): the slot is the instance's index inside its Gaussian's rect (render_bwd adds
+                // emit_start[id], which it loads anyway: no gather of the record start behind the id here)
+                const uint2 v = make_uint2(local, s.id[j]);
                 if (J.pack_shift) {
                     if (J.soa_y) {
                         if (J.soa_x) J.soa_x[dst] = v.x;  // (no slot array: slots_from_rect)
@@ -1208,32 +1109,22 @@ __global__ void __launch_bounds__(256) debug_keys_kernel(int L, const uint32_t* 
     keys[idx] = ((uint64_t)sorted_tiles[idx] << 32) | dkeys[point_list[idx]];
 }
 
-static inline int rs_items(int n) { return n <= RS_SHORT_MAX ? RS_ITEMS_SHORT : RS_ITEMS; }
 static inline size_t rs_chunks_tile(int n, int tile) { return ((size_t)(n > 0 ? n : 0) + tile - 1) / tile; }
-static inline size_t rs_chunks(int n)
-{
-    const size_t tile = (size_t)RS_THREADS * rs_items(n);
-    return ((size_t)(n > 0 ? n : 0) + tile - 1) / tile;
-}
+static inline size_t rs_chunks(int n) { return rs_chunks_tile(n, RS_THREADS * RS_ITEMS); }
 
 // Scratch of one sort: the (bins x chunks) count matrix and the bin totals (reused by every pass),
 // then the per-chunk key min / max and the RangeWord of a three-pass depth sort.
 static inline size_t rs_count_bytes(int n) { return align_up(rs_chunks(n) * RS_SCRATCH_BINS * 4 + 256, 256); }
 static inline size_t rs_totals_bytes() { return align_up(RS_SCRATCH_BINS * 4, 256); }
-// ... then the chunk-group digit counts of the three passes of a depth sort (GSR_DEPTH_GSUM)
+// ... then the chunk-group digit counts of the three passes of a depth sort (GS_CHUNKS)
 static inline size_t rs_gsum_stride(int n)
 {
     return align_up((rs_chunks(n) + GS_CHUNKS - 1) / GS_CHUNKS * RS_SCRATCH_BINS * 4, 256);
 }
 size_t radix_gsum_offset(int n) { return rs_count_bytes(n) + rs_totals_bytes() + align_up(2 * rs_chunks(n) * 4 + 64, 256); }
 size_t radix_gsum_bytes(int n) { return 3 * rs_gsum_stride(n); }  // (DEPTH3_PASSES)
-size_t radix_status_bytes(int n, int npass)
-{
-    (void)npass;
-    return radix_gsum_offset(n) + radix_gsum_bytes(n);
-}
-static_assert(RS_THREADS * RS_ITEMS == 2048 && RS_THREADS * RS_ITEMS_SHORT == 2048 && RS_MAXBINS == 256,
-              "2,048-key chunks");
+size_t radix_status_bytes(int n) { return radix_gsum_offset(n) + radix_gsum_bytes(n); }
+static_assert(RS_THREADS * RS_ITEMS == 2048 && RS_MAXBINS == 256, "2,048-key chunks");
 
 // Full LSD sort of n u32 keys over bits [0, nbits), stable.  Payload: the input index i, or with
 // `pairs` the u32x2 pairs[i].  Ping-pongs between (k0,v0) and (k1,v1) (v: u32, or u32x2 with
@@ -1272,18 +1163,18 @@ static inline uint32_t* sort_gsum(const SortJob& j, int pass)
 }
 
 // (2) for a pass of nbins digits over (up to) maxc chunks: the per-digit exclusive scans over the
-// chunks and the digit totals (+ the range workgroup)
-static inline bool chunk_major(int maxc) { return GSR_COLSCAN && maxc <= CS_CHUNKS; }
+// chunks and the digit totals
+static inline bool chunk_major(int maxc) { return maxc <= CS_CHUNKS; }
 template <typename KIND>
-static void launch_scan_rows(const ViewBatch<RowJob>& rb, int nv, int nbins, int maxc, bool range, hipStream_t s)
+static void launch_scan_rows(const ViewBatch<RowJob>& rb, int nv, int nbins, int maxc, hipStream_t s)
 {
     const dim3 b(RS_THREADS);
     if (chunk_major(maxc)) {
-        const dim3 g((unsigned)((nbins + CS_DIG - 1) / CS_DIG + (range ? 1 : 0)), (unsigned)nv);
+        const dim3 g((unsigned)((nbins + CS_DIG - 1) / CS_DIG), (unsigned)nv);
         hipLaunchKernelGGL(radix_colscan_kernel<KIND>, g, b, 0, s, rb);
         return;
     }
-    const dim3 g((unsigned)(nbins + (range ? 1 : 0)), (unsigned)nv);
+    const dim3 g((unsigned)nbins, (unsigned)nv);
     if (maxc <= RS_ROW_LDS)
         hipLaunchKernelGGL(radix_rowscan_lds_kernel<KIND>, g, b, 0, s, rb);
     else
@@ -1301,13 +1192,10 @@ struct PassSpec { int w, shift, mode; };
 // minimum (DigitMode); after a range that did not fit (four_pass), four 8-bit passes.
 constexpr int DEPTH3_PASSES = 3;  // (radix_gsum_bytes: one group matrix per pass)
 constexpr PassSpec DEPTH3[DEPTH3_PASSES] = {{9, 0, DIG_RAW}, {9, 9, DIG_RAW}, {9, 18, DIG_REL}};
-#ifndef GSR_DEPTH3
-#define GSR_DEPTH3 1
-#endif
 // test hook (gsr_debug_set_depth_wide): this host thread's depth sorts run four passes
 static thread_local bool t_force_wide = false;
 void set_depth_force_wide(bool on) { t_force_wide = on; }
-bool depth_force_wide() { return t_force_wide || !GSR_DEPTH3; }
+bool depth_force_wide() { return t_force_wide; }
 
 template <typename KIND>
 static hipError_t radix_sort_batch_k(const SortJob* jobs, int V, int nbits, hipStream_t s, int shift0, bool four_pass)
@@ -1316,7 +1204,7 @@ static hipError_t radix_sort_batch_k(const SortJob* jobs, int V, int nbits, hipS
     const bool depth3 = !four_pass && !depth_force_wide() && nbits == 32 && shift0 == 0 &&
                         std::is_same<KIND, DepthSort>::value;
     const int npass = depth3 ? DEPTH3_PASSES : (nbits + 7) / 8;
-    const bool gsum = depth3 && GSR_DEPTH_GSUM;  // no column-scan launches (see GS_CHUNKS)
+    const bool gsum = depth3;  // the group-sum sort: no scan launches (see GS_CHUNKS)
     return for_groups(V, [&](int v0, int nv) -> hipError_t {
         if (gsum)
             for (int v = 0; v < nv; v++) {
@@ -1385,17 +1273,10 @@ static hipError_t radix_sort_batch_k(const SortJob* jobs, int V, int nbits, hipS
                         cb.v[v].host_wide = j.host_wide;
                     }
                 }
-                rb.v[v] = {sort_counts(j), nchunks, sort_totals(j)};
+                rb.v[v] = {sort_counts(j), nchunks, sort_totals(j), 1 << w};
                 if (depth3 && p == 0) {  // the keys' range, for the relative pass
                     cb.v[v].cmin = sort_minmax(j);
                     cb.v[v].cmax = sort_minmax(j) + nchunks;
-                    rb.v[v].cmin = cb.v[v].cmin;
-                    rb.v[v].cmax = cb.v[v].cmax;
-                    rb.v[v].range_out = sort_range(j);
-                    rb.v[v].nbins = 1 << w;
-                    rb.v[v].rel_shift = DEPTH3[2].shift;
-                    rb.v[v].rel_bits = DEPTH3[2].w;
-                    rb.v[v].host_wide = j.host_wide;
                 }
                 SortPassArgs& a = sb.v[v];
                 a.n = j.n;
@@ -1430,8 +1311,7 @@ static hipError_t radix_sort_batch_k(const SortJob* jobs, int V, int nbits, hipS
                 hipLaunchKernelGGL((radix_count_kernel<RS_ITEMS, KIND, 512, RS_THREADS_WIDE>), g, bw, 0, s, cb, shift, w);
             else
                 hipLaunchKernelGGL((radix_count_kernel<RS_ITEMS, KIND, RS_MAXBINS>), g, b, 0, s, cb, shift, w);
-            for (int v = 0; v < nv; v++) rb.v[v].nbins = 1 << w;
-            if (!gsum) launch_scan_rows<KIND>(rb, nv, 1 << w, maxc_p, depth3 && p == 0, s);
+            if (!gsum) launch_scan_rows<KIND>(rb, nv, 1 << w, maxc_p, s);
             if (wide) {
                 if (pair)
                     hipLaunchKernelGGL((radix_scatter_kernel<RS_ITEMS, true, KIND, 9, RS_THREADS_WIDE>), gs, bw, 0, s, sb);
@@ -1465,10 +1345,6 @@ hipError_t radix_sort_batch(const SortJob* jobs, int V, int nbits, hipStream_t s
     }
 }
 
-#ifndef GSR_TILE_W1_DELTA
-#define GSR_TILE_W1_DELTA -1
-#endif
-
 size_t fused_pass1_scratch_bytes(int P)
 {
     const size_t chunks = ((size_t)(P > 0 ? P : 0) + FE_RANKS - 1) / FE_RANKS;
@@ -1483,7 +1359,7 @@ hipError_t tile_sort_fused_batch(const TileSortJob* jobs, int V, uint32_t gx, in
     // (the fused pass costs more per digit bit than the plain second one: 6 + 7 bits at 1080p measured
     // 480-487 us per 8-view tile sort against 490-493 for 7 + 6, and 8 + 5 567-579)
     int w1 = nbits / npass + (nbits % npass ? 1 : 0);
-    if (npass == 2) w1 = min(max(w1 + GSR_TILE_W1_DELTA, nbits - 8), 8);
+    if (npass == 2) w1 = min(max(w1 - 1, nbits - 8), 8);
     return for_groups(V, [&](int v0, int nv) -> hipError_t {
         ViewBatch<FusedPassArgs> fb;
         ViewBatch<RowJob> rb;
@@ -1500,7 +1376,6 @@ hipError_t tile_sort_fused_batch(const TileSortJob* jobs, int V, uint32_t gx, in
             a.sorted_ids = j.sorted_ids;
             a.offsets = j.offsets;
             a.sorted_rects = j.sorted_rects;
-            a.rec_start = j.rec_start;
             a.counts = reinterpret_cast<uint32_t*>(j.pass1_scratch);
             a.totals = reinterpret_cast<uint32_t*>(j.pass1_scratch +
                                                    align_up((size_t)a.nchunks * RS_MAXBINS * 4 + 256, 256));
@@ -1513,20 +1388,19 @@ hipError_t tile_sort_fused_batch(const TileSortJob* jobs, int V, uint32_t gx, in
             a.pack_shift = 0;
             a.pack_w1 = w1;
             a.soa_x = a.soa_y = nullptr;
-            if (GSR_TILE_PACK && npass == 2 && !j.out_tiles && (uint64_t)j.P <= (1ull << (32 - (nbits - w1)))) {
+            if (npass == 2 && !j.out_tiles && (uint64_t)j.P <= (1ull << (32 - (nbits - w1)))) {
                 a.pack_shift = 32 - (nbits - w1);
                 a.keys_out = nullptr;
-                if (GSR_TILE_SOA) {  // the v1 ping-pong region (8 B per instance) as two 4-B arrays
-                    a.soa_x = j.slotless ? nullptr : j.v1;
-                    a.soa_y = j.v1 + align_up(4 * (size_t)(j.L > 0 ? j.L : 0), 256) / 4;
-                }
+                // the v1 ping-pong region (8 B per instance) as two 4-B arrays
+                a.soa_x = j.slotless ? nullptr : j.v1;
+                a.soa_y = j.v1 + align_up(4 * (size_t)(j.L > 0 ? j.L : 0), 256) / 4;
             }
             a.out_slot = j.slotless ? nullptr : j.out_slot;
             a.out_ids = j.out_ids;
             a.out_tiles = j.out_tiles;
             a.valid = j.valid;
             a.ranges = j.ranges;
-            rb.v[v] = {a.counts, a.nchunks, a.totals};
+            rb.v[v] = {a.counts, a.nchunks, a.totals, 1 << w1};
             maxc = max(maxc, a.nchunks);
             rest[v] = {j.L, a.pack_shift ? nullptr : j.k1, reinterpret_cast<const uint2*>(j.v1), j.k0, j.v0, j.k1, j.v1,
                        j.out_slot, j.out_ids, j.out_tiles, j.scratch, nullptr, nullptr, nullptr};
@@ -1543,9 +1417,8 @@ hipError_t tile_sort_fused_batch(const TileSortJob* jobs, int V, uint32_t gx, in
         const dim3 g((unsigned)maxc, (unsigned)nv), b(RS_THREADS);
         if (phases & FUSED_COUNT) {
             hipLaunchKernelGGL(fused_pass1_count_kernel, g, b, 0, s, fb, gx, T, w1);
-            for (int v = 0; v < nv; v++) rb.v[v].nbins = 1 << w1;
             // (the fused pass's count matrix is digit-major: thousands of 256-rank chunks)
-            launch_scan_rows<TileSort>(rb, nv, 1 << w1, max(maxc, CS_CHUNKS + 1), false, s);
+            launch_scan_rows<TileSort>(rb, nv, 1 << w1, max(maxc, CS_CHUNKS + 1), s);
         }
         if (!(phases & FUSED_SCATTER)) return hipGetLastError();
         const dim3 gs((unsigned)maxc, (unsigned)nv);

@@ -707,16 +707,12 @@ __device__ __forceinline__ void bwd_lane_terms(const BwdAcc& o, float dy, float*
 // reduction: 0.79 bank-conflict cycles per LDS instruction at random entries; -1 %.)  Against one
 // 64-lane pass per entry over the half-tiles it reaches, this skips the pixel pairs of quadrants
 // an entry does not reach (25 % of them) and reduces over 16 lanes: render_bwd -11 %.
-// Tiles (independent waves) per workgroup.  Round 2 chose 4: a retiring 4-wave workgroup frees one
+// One tile (one wave) per workgroup.  Round 2 chose 4 tiles (independent waves): a retiring 4-wave workgroup frees one
 // wave slot on each SIMD of its CU -- the footprint of a 256-thread binning-prefix workgroup of the
 // next view, which then ran beside this launch when views alternated over two streams (1 -> 2 -> 4
 // -> 8 tiles: 2,258 / 2,285 / 2,340 / 2,323 Mpix/s then).  Since the views are batched, the prefix
 // runs before the renders and nothing needs that hole: one tile per workgroup (the finest dispatch
 // granularity) measured render_bwd 1,910-1,915 -> 1,873-1,883 us per 8 views (round 5, 3 rounds).
-#ifndef GSR_BWD_TPW
-#define GSR_BWD_TPW 1
-#endif
-constexpr int BWD_TPW = GSR_BWD_TPW;
 // reduction blocks of partial rows per wave: 11 blocks = 33 iterations per pass (5.5 KB per wave)
 #ifndef GSR_BWD_PART_BLOCKS
 #define GSR_BWD_PART_BLOCKS 11
@@ -734,16 +730,15 @@ static_assert(BWD_PART_STRIDE >= 128 && BWD_PART_STRIDE % 2 == 0, "partial rows:
 // slower; entry jj + 1's staged record read from LDS while entry jj computes, 2 % slower.)
 
 template <bool HAS_INV>
-__global__ void __launch_bounds__(64 * BWD_TPW) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVES))) render_bwd_kernel(const ViewBatch<RenderBwdArgs> B)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVES))) render_bwd_kernel(const ViewBatch<RenderBwdArgs> B)
 {
 #pragma clang fp contract(fast)
     const RenderBwdArgs& a = B.v[blockIdx.y];  // a batch of views: one launch tail per batch
     constexpr int G = 3;  // entries per group and transposed reduction (3 x 10 gradient terms <= 32 values)
     // a pass evaluates <= 32 entries per quadrant (the two-pass split below): they must fit the rows
     static_assert(G * BWD_PART_BLOCKS >= 32, "partial rows: a half batch's 32 entries per quadrant");
-    const int wv = BWD_TPW == 1 ? 0 : (int)(threadIdx.x >> 6);
-    const int ti = (int)blockIdx.x * BWD_TPW + wv;
-    if (ti >= a.T) return;  // waves are independent: no workgroup barrier below
+    const int ti = (int)blockIdx.x;
+    if (ti >= a.T) return;
     const uint32_t tile = a.tile_order[ti];
     const uint32_t tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int lane = (int)(threadIdx.x & 63);
@@ -802,8 +797,8 @@ __global__ void __launch_bounds__(64 * BWD_TPW) __attribute__((amdgpu_waves_per_
     // scalar load beside the range's, so the first batch's list loads do not wait for the pixel state
     const uint32_t tmax = a.tile_work[tile];
 
-    __shared__ float4 s_recw[BWD_TPW][3][64];
-    __shared__ uint8_t s_lqw[BWD_TPW][4][64];
+    __shared__ float4 s_rec[3][64];
+    __shared__ uint8_t s_lq[4][64];  // per quadrant: the batch entries it evaluates, in list order
     // The groups' partial totals, one 32-float row per (reduction block, group): block b holds the
     // group's iterations 3b .. 3b + 2 (value jj * GF_NUM + f = term f of iteration 3b + jj).  Every
     // reduction writes its block with ONE conflict-free 8-B store per lane (the 64 lanes cover 512
@@ -812,10 +807,8 @@ __global__ void __launch_bounds__(64 * BWD_TPW) __attribute__((amdgpu_waves_per_
     // block b at a lane-dependent b, and with a 128-float stride (0 mod the 64 banks) the up to 33
     // lanes reading one quadrant's partials fell into 3 banks -- 11-way conflicts; 132 spreads them
     // to 2 LDS cycles, the minimum for 64 lanes x 8 B)
-    __shared__ __attribute__((aligned(16))) float s_partw[BWD_TPW][BWD_PART_BLOCKS * BWD_PART_STRIDE];
-    float4 (&s_rec)[3][64] = s_recw[wv];
-    uint8_t (&s_lq)[4][64] = s_lqw[wv];  // per quadrant: the batch entries it evaluates, in list order
-    float* s_part = s_partw[wv];  // block b, group g, value k at b * BWD_PART_STRIDE + 32 g + k
+    // block b, group g, value k at b * BWD_PART_STRIDE + 32 g + k
+    __shared__ __attribute__((aligned(16))) float s_part[BWD_PART_BLOCKS * BWD_PART_STRIDE];
 
     // Only the quadrants in which an entry contributed to some pixel in the forward (render_fwd's
     // a.hit bits: alpha >= 1/255 and the pixel not yet saturated, the tests this loop repeats per
@@ -848,7 +841,7 @@ __global__ void __launch_bounds__(64 * BWD_TPW) __attribute__((amdgpu_waves_per_
         if (m != 0) {
             const float4* r = a.splat + 3 * (size_t)id;
             const float4 r0 = r[0], r1 = r[1], r2 = r[2];
-            if (GSR_REC_MASK || GSR_SLOT_LOCAL) es = a.emit_start[id];
+            es = a.emit_start[id];
             if (!a.slot) myslot = rect_local(__float_as_uint(r0.w), tx, ty);
             s_rec[0][lane] = r0;
             s_rec[1][lane] = r1;
@@ -952,24 +945,18 @@ __global__ void __launch_bounds__(64 * BWD_TPW) __attribute__((amdgpu_waves_per_
                         }
                     }
                 }
-                const uint32_t slot = GSR_SLOT_LOCAL ? es + myslot : myslot;  // (BIN_SLOT: the index in the rect)
+                const uint32_t slot = es + myslot;  // (BIN_SLOT: the index in the rect)
                 float* rec = a.grad_inst + (size_t)slot * GRAD_REC;
                 float t[GF_NUM];
 #pragma unroll
                 for (int f = 0; f < GF_NUM; f++) t[f] = t0[f] + t1[f];
-                if constexpr (GRAD_REC % 4 == 0) {  // 16-B aligned records
-                    reinterpret_cast<float4*>(rec)[0] = make_float4(t[0], t[1], t[2], t[3]);
-                    reinterpret_cast<float4*>(rec)[1] = make_float4(t[4], t[5], t[6], t[7]);
-                    reinterpret_cast<float2*>(rec)[4] = make_float2(t[8], t[9]);
-                } else {  // packed 40-B records: 8-B aligned
-#pragma unroll
-                    for (int h = 0; h < GF_NUM / 2; h++) reinterpret_cast<float2*>(rec)[h] = make_float2(t[2 * h], t[2 * h + 1]);
-                }
+#pragma unroll  // packed 40-B records: 8-B aligned
+                for (int h = 0; h < GF_NUM / 2; h++) reinterpret_cast<float2*>(rec)[h] = make_float2(t[2 * h], t[2 * h + 1]);
                 // flagged in the Gaussian's own mask when it is one of its first 32 slots (preprocess_bwd
                 // then finds the records without a dependent load of the valid words), else in the valid
                 // words: one atomic per record either way
                 const uint32_t local = slot - es;
-                if (GSR_REC_MASK && local < 32u) atomicOr(&a.rec_mask[id], 1u << local);
+                if (local < 32u) atomicOr(&a.rec_mask[id], 1u << local);
                 else atomicOr(&a.valid[slot >> 5], 1u << (slot & 31u));
             }
             __builtin_amdgcn_wave_barrier();  // s_rec / s_lq / s_part reuse in the next pass
@@ -1037,7 +1024,7 @@ hipError_t launch_render_bwd_batch(const RenderBwdArgs* a, int V, int T, hipStre
         }
         for (int v = 0; v < B.n; v++)  // one kernel variant per launch: all views with or without invdepth
             if ((B.v[v].dL_invdepths != nullptr) != inv) return hipErrorInvalidValue;
-        const dim3 grid((unsigned)((T + BWD_TPW - 1) / BWD_TPW), (unsigned)B.n), block(64 * BWD_TPW);
+        const dim3 grid((unsigned)T, (unsigned)B.n), block(64);
         if (inv) hipLaunchKernelGGL(render_bwd_kernel<true>, grid, block, 0, s, B);
         else hipLaunchKernelGGL(render_bwd_kernel<false>, grid, block, 0, s, B);
         const hipError_t e = hipGetLastError();

@@ -721,7 +721,7 @@ def set_depth_wide(on):
 
 
 def grad_record_floats():
-    """Floats per per-instance gradient record (GSR_GRAD_REC of the library build; diagnostics)."""
+    """Floats per per-instance gradient record (10 = 40 B; diagnostics)."""
     return int(lib.gsr_debug_grad_record_floats())
 
 

@@ -375,7 +375,7 @@ int gsr_adam_update_multi(int n_groups, float* const* params, const float* const
  * work (record-slot scan, tile histogram, forward tile order) on a second internal stream;
  * on = 2: on the caller's stream, the side work on the internal one (no join before render_fwd);
  * on = 0: every launch on the caller's stream.  Other values: GSR_ERR_INVALID.  Per host
- * thread; the default is the library's build-time GSR_PREFIX_MODE_DEFAULT. */
+ * thread; the default is 1. */
 int gsr_set_prefix_stream(int on);
 
 /* Debug / parity helper: writes the sorted 64-bit tile|depth keys
@@ -406,8 +406,8 @@ int gsr_debug_depth_wide(void);
 int gsr_debug_set_depth_wide(int on);
 int gsr_debug_last_depth_passes(int view);
 
-/* Floats per per-instance gradient record in the binning buffer's GRAD_INST region (the build's
- * GSR_GRAD_REC: 10 = 40 B), for diagnostics that decode the records. */
+/* Floats per per-instance gradient record in the binning buffer's GRAD_INST region (10 = 40 B),
+ * for diagnostics that decode the records. */
 int gsr_debug_grad_record_floats(void);
 
 /* Byte offsets of the arrays inside each opaque state buffer (n entries
