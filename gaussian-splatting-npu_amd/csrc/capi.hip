@@ -1495,6 +1495,78 @@ int gsr_ssim_backward(int planes, int H, int W, float C1, float C2, const float*
     return GSR_OK;
 }
 
+// the loss entry points' shared argument checks (no HIP call); *empty: a zero size, nothing to do
+static int photo_loss_args(int V, int C, int H, int W, float lambda_dssim, const float* const* gt, bool* empty,
+                           PhotoViews* out)
+{
+    *empty = true;
+    if (V < 0 || C < 0 || H < 0 || W < 0) return fail(GSR_ERR_INVALID, "negative image size");
+    if (V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be <= 16");
+    if (!(lambda_dssim >= 0.f && lambda_dssim <= 1.f)) return fail(GSR_ERR_INVALID, "lambda_dssim must be in [0, 1]");
+    if ((size_t)V * C == 0 || (size_t)H * W == 0) return GSR_OK;
+    if ((size_t)V * C > 0x7FFFFFFFu) return fail(GSR_ERR_INVALID, "too many planes");
+    if (!gt) return fail(GSR_ERR_INVALID, "null pointer");
+    out->V = V;
+    out->C = C;
+    for (int v = 0; v < MAX_VIEWS; v++) {
+        if (v < V && !gt[v]) return fail(GSR_ERR_INVALID, "null ground-truth pointer");
+        out->gt[v] = v < V ? gt[v] : nullptr;
+    }
+    *empty = false;
+    return GSR_OK;
+}
+
+size_t gsr_photo_loss_workspace_size(int V, int C, int H, int W)
+{
+    return V > MAX_VIEWS ? 0 : photo_loss_workspace_bytes(V, C, H, W);
+}
+
+int gsr_photo_loss_forward(int V, int C, int H, int W, float lambda_dssim, int clamp, const float* img,
+                           const float* const* gt, float* loss, float* dm_dmu1, float* dm_dsigma1_sq,
+                           float* dm_dsigma12, void* workspace, void* stream)
+{
+    PhotoViews pv;
+    bool empty;
+    const int rc = photo_loss_args(V, C, H, W, lambda_dssim, gt, &empty, &pv);
+    if (rc || empty) return rc;
+    if (!img || !loss || !workspace) return fail(GSR_ERR_INVALID, "null pointer");
+    const bool train = dm_dmu1 && dm_dsigma1_sq && dm_dsigma12;
+    HIP_TRY(launch_photo_loss_fwd(pv, H, W, lambda_dssim, clamp != 0, img, loss, train ? dm_dmu1 : nullptr,
+                                  train ? dm_dsigma1_sq : nullptr, train ? dm_dsigma12 : nullptr, workspace,
+                                  (hipStream_t)stream));
+    return GSR_OK;
+}
+
+int gsr_photo_loss_backward(int V, int C, int H, int W, float lambda_dssim, int clamp, const float* img,
+                            const float* const* gt, const float* dL_dloss, const float* dm_dmu1,
+                            const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_dimg, void* stream)
+{
+    PhotoViews pv;
+    bool empty;
+    const int rc = photo_loss_args(V, C, H, W, lambda_dssim, gt, &empty, &pv);
+    if (rc || empty) return rc;
+    if (!img || !dL_dloss || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_dimg)
+        return fail(GSR_ERR_INVALID, "null pointer");
+    HIP_TRY(launch_photo_loss_bwd(pv, H, W, lambda_dssim, clamp != 0, img, dL_dloss, dm_dmu1, dm_dsigma1_sq,
+                                  dm_dsigma12, dL_dimg, (hipStream_t)stream));
+    return GSR_OK;
+}
+
+// ---- densification statistics (densify_stats.hip) ----
+int gsr_densification_stats(int V, int P, const float* viewspace_grads, const int* radii, float* max_radii2D,
+                            float* accum, long accum_stride, float* denom, long denom_stride,
+                            float* visible_count, gsr_stream_t stream)
+{
+    if (V < 0 || P < 0) return fail(GSR_ERR_INVALID, "V and P must be >= 0");
+    if (accum_stride < 1 || denom_stride < 1) return fail(GSR_ERR_INVALID, "strides must be >= 1");
+    if (V == 0 || P == 0) return GSR_OK;
+    if (!viewspace_grads || !radii || !max_radii2D || !accum || !denom) return fail(GSR_ERR_INVALID, "null pointer");
+    const DensifyStatsArgs a = {V, P, viewspace_grads, radii, max_radii2D, accum, denom, accum_stride, denom_stride,
+                                visible_count};
+    HIP_TRY(launch_densify_stats(a, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 // ---- simple_knn.h ----
 size_t gsr_knn_workspace_size(int P) { return knn_workspace_bytes(P); }
 

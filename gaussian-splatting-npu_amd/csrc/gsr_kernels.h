@@ -338,6 +338,39 @@ hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const f
 hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const float* img2, const float* dmap,
                            const float* dA, const float* dB, const float* dC, float* dimg1, hipStream_t s);
 
+// fused photometric loss of V views of C planes each (ssim.hip):
+//   loss[v] = (1 - lambda) mean|x - gt_v| + lambda (1 - mean SSIM(x, gt_v)),  x = img or clamp(img, 0, 1).
+// img / dimg / dA..dC: contiguous (V, C, H, W); gt: one (C, H, W) array per view.
+struct PhotoViews {
+    const float* gt[MAX_VIEWS];
+    int V, C;
+};
+// bytes of the forward's workspace (one (sum SSIM, sum |x - gt|) pair of doubles per tile)
+size_t photo_loss_workspace_bytes(int V, int C, int H, int W);
+// dA/dB/dC null: no backward will follow (nothing but loss[V] is written)
+hipError_t launch_photo_loss_fwd(const PhotoViews& views, int H, int W, float lambda, bool clamp, const float* img,
+                                 float* loss, float* dA, float* dB, float* dC, void* workspace, hipStream_t s);
+// dloss: V upstream gradients on the device
+hipError_t launch_photo_loss_bwd(const PhotoViews& views, int H, int W, float lambda, bool clamp, const float* img,
+                                 const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
+                                 hipStream_t s);
+
+// densification statistics of V views in one pass (densify_stats.hip): for every Gaussian i and every
+// view v in order with radii[v, i] > 0: max_radii[i] = max(max_radii[i], radii[v, i]),
+// accum[i] += |grads[v, i, 0:2]|, denom[i] += 1, visible_count[i] += 1 (if given).  accum / denom are
+// addressed with element strides; Gaussians no view sees are not written.
+struct DensifyStatsArgs {
+    int V, P;
+    const float* grads;  // (V, P, 3)
+    const int* radii;    // (V, P)
+    float* max_radii;    // (P,)
+    float* accum;
+    float* denom;
+    long accum_stride, denom_stride;
+    float* visible_count;  // (P,) or null
+};
+hipError_t launch_densify_stats(const DensifyStatsArgs& a, hipStream_t s);
+
 // distCUDA2 (knn.hip); host_bounds: 6 words of pinned host memory
 size_t knn_workspace_bytes(int P);
 hipError_t knn_dist2(int P, const float* pts, float* dist2, char* workspace, uint32_t* host_bounds, hipStream_t s);

@@ -268,6 +268,275 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(SsGrid g, SsimWeights wt,
     }
 }
 
+// ---- fused photometric loss of a batch of views (train.py:119-124) ---------------------------------
+// loss[v] = (1 - lambda) mean|x - gt_v| + lambda (1 - mean SSIM(x, gt_v)), x = img or clamp(img, 0, 1).
+// The forward is ssim_fwd_kernel's pass over the planes of ALL views in one launch, but instead of
+// the map it reduces each tile's sum of SSIM and of |x - gt| (the centre pixels are in LDS already)
+// to one pair of doubles per tile; photo_loss_reduce_kernel then adds each view's pairs in a fixed
+// order.  The backward applies the window to the three partial planes alone: the upstream gradient
+// of the map is the per-view constant -lambda / N * dL/dloss[v], applied after the (linear) window,
+// and the L1 term and the clamp mask are finished in the same store.  Per plane-pixel the two
+// kernels move 11 floats (img, gt in; 3 planes out -- 3 planes, img, gt in; dL/dimg out).
+
+// Tile t of the loss kernels: plane z = v C + c of the contiguous (V, C, H, W) arrays, and channel c
+// of view v's own ground truth.
+struct PhotoTile {
+    SsTile at;         // plane = the offset into the contiguous arrays
+    SsTile local;      // the same tile with plane 0, for loads through img / gt below
+    const float* img;  // the tile's plane of img
+    const float* gt;   // the tile's plane of the view's ground truth
+    int v;
+};
+
+__device__ __forceinline__ PhotoTile photo_tile(const SsGrid& g, const PhotoViews& pv, const float* img, int t)
+{
+    const SsTile a = ss_tile(g, t);
+    const int z = t / (g.tx * g.ty);
+    const int v = z / pv.C, c = z - v * pv.C;
+    return {a, {0, a.x0, a.y0}, img + a.plane, pv.gt[v] + (size_t)c * g.H * g.W, v};
+}
+
+__device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
+// lane 0 of each wave: the sum over its 64 lanes, in a fixed order
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    return x;
+}
+
+// dA null: the loss alone (no backward will follow).  Two waves per SIMD (= SS_BLOCKS_PER_CU
+// workgroups per CU): without the bound the allocator takes 263 registers and one workgroup fits.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+photo_loss_fwd_kernel(SsGrid g, PhotoViews pv, float C1, float C2, SsimWeights wt, int clamp, const float* img,
+                      float* dA, float* dB, float* dC, double2* partial)
+{
+    __shared__ float s1[SS_STAGE], s2[SS_STAGE];
+    __shared__ f2 hs[5][SS_HH][32];  // horizontal pass per column pair: x, y, xx, yy, xy
+    __shared__ double red[4][2];
+    const int p = threadIdx.x & 31, q = threadIdx.x >> 5;
+    int t = blockIdx.x;
+    if (t >= g.ntiles) return;  // uniform over the workgroup
+    SsHalo<2> halo;
+    {
+        const PhotoTile n = photo_tile(g, pv, img, t);
+        const float* const src[2] = {n.img, n.gt};
+        halo.load(src, g, n.local);
+    }
+    for (; t < g.ntiles; t += gridDim.x) {
+        const PhotoTile cur = photo_tile(g, pv, img, t);
+        __syncthreads();  // the previous tile is done with s1, s2, hs and red
+#pragma unroll
+        for (int j = 0; j < SS_STAGE_IT; j++) {
+            const int i = threadIdx.x + j * 256;
+            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+            const float a = halo.get(0, j);
+            s1[i] = clamp ? clamp01(a) : a;
+            s2[i] = halo.get(1, j);
+        }
+        if (t + (int)gridDim.x < g.ntiles) {
+            const PhotoTile n = photo_tile(g, pv, img, t + gridDim.x);
+            const float* const src[2] = {n.img, n.gt};
+            halo.load(src, g, n.local);
+        }
+        __syncthreads();
+        for (int r = q; r < SS_HH; r += 8) {
+            f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
+            const float* r1 = s1 + r * SS_LS + p;
+            const float* r2 = s2 + r * SS_LS + p;
+#pragma unroll
+            for (int k = 0; k < 11; k++) {
+                const f2 a = {r1[k], r1[k + 32]}, b = {r2[k], r2[k + 32]};
+                const float w = wt.w[k];
+                mx = pk_fma(w, a, mx);
+                my = pk_fma(w, b, my);
+                mxx = pk_fma(w, a * a, mxx);
+                myy = pk_fma(w, b * b, myy);
+                mxy = pk_fma(w, a * b, mxy);
+            }
+            hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
+        }
+        __syncthreads();
+        f2 m4[4][5];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int k = 0; k < 5; k++) m4[i][k] = f2{0.f, 0.f};
+#pragma unroll
+        for (int rr = 0; rr < 14; rr++) {
+            f2 v[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) v[k] = hs[k][4 * q + rr][p];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int tap = rr - i;
+                if (tap < 0 || tap > 10) continue;
+#pragma unroll
+                for (int k = 0; k < 5; k++) m4[i][k] = pk_fma(wt.w[tap], v[k], m4[i][k]);
+            }
+        }
+        // this thread's 8 pixels (float: 8 terms of at most 1; the sums over threads and tiles are double)
+        float ssim8 = 0.f, l18 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int y = cur.at.y0 + 4 * q + i;
+            if (y >= g.H) break;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int x = cur.at.x0 + p + 32 * h;
+                if (x >= g.W) continue;
+                const float mu1 = m4[i][0][h], mu2 = m4[i][1][h];
+                const float s11 = m4[i][2][h] - mu1 * mu1, s22 = m4[i][3][h] - mu2 * mu2;
+                const float s12 = m4[i][4][h] - mu1 * mu2;
+                const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
+                const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
+                const float inv = 1.f / (Cc * D);
+                const float val = A * B * inv;
+                const int c = (4 * q + i + SS_R) * SS_LS + p + 32 * h + SS_R;  // the pixel itself in the halo
+                ssim8 += val;
+                l18 += fabsf(s1[c] - s2[c]);
+                if (dA) {
+                    const size_t o = cur.at.plane + (size_t)y * g.W + x;
+                    const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
+                    const float f_s11 = -val * Cc * inv;
+                    const float f_s12 = 2.f * A * inv;
+                    dA[o] = f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12;
+                    dB[o] = f_s11;
+                    dC[o] = f_s12;
+                }
+            }
+        }
+        const double sum_ssim = wave_sum((double)ssim8), sum_l1 = wave_sum((double)l18);
+        if ((threadIdx.x & 63) == 0) {
+            red[threadIdx.x >> 6][0] = sum_ssim;
+            red[threadIdx.x >> 6][1] = sum_l1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partial[t] = double2{((red[0][0] + red[1][0]) + red[2][0]) + red[3][0],
+                                 ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]};
+    }
+}
+
+// One workgroup per view: its tiles' pairs, added in an order that depends on nothing but the shape.
+__global__ void __launch_bounds__(256) photo_loss_reduce_kernel(const double2* partial, int tiles_per_view,
+                                                                double inv_n, double lambda, float* loss)
+{
+    __shared__ double red[4][2];
+    const double2* pv = partial + (size_t)blockIdx.x * tiles_per_view;
+    double sum_ssim = 0.0, sum_l1 = 0.0;
+    for (int k = threadIdx.x; k < tiles_per_view; k += 256) {
+        const double2 e = pv[k];
+        sum_ssim += e.x;
+        sum_l1 += e.y;
+    }
+    sum_ssim = wave_sum(sum_ssim);
+    sum_l1 = wave_sum(sum_l1);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = sum_ssim;
+        red[threadIdx.x >> 6][1] = sum_l1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double ssim = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) * inv_n;
+        const double l1 = (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]) * inv_n;
+        loss[blockIdx.x] = (float)((1.0 - lambda) * l1 + lambda * (1.0 - ssim));
+    }
+}
+
+// dL/dimg = dloss[v] (k_ssim (w * A + 2 x w * B + gt w * C) + k_l1 sign(x - gt)), k_ssim = -lambda / N,
+// k_l1 = (1 - lambda) / N; zero where the clamp is active.
+__global__ void __launch_bounds__(256) photo_loss_bwd_kernel(SsGrid g, PhotoViews pv, SsimWeights wt, int clamp,
+                                                             float k_ssim, float k_l1, const float* img,
+                                                             const float* dloss, const float* dA, const float* dB,
+                                                             const float* dC, float* dimg)
+{
+    __shared__ float gs[3][SS_STAGE];  // A, B, C over the halo (zero outside)
+    __shared__ f2 hs[3][SS_HH][32];
+    const int p = threadIdx.x & 31, q = threadIdx.x >> 5;
+    const float* const src[3] = {dA, dB, dC};
+    int t = blockIdx.x;
+    if (t >= g.ntiles) return;
+    SsHalo<3> halo;
+    halo.load(src, g, ss_tile(g, t));
+    for (; t < g.ntiles; t += gridDim.x) {
+        const PhotoTile cur = photo_tile(g, pv, img, t);
+        const float gv = dloss[cur.v];
+        // this thread's output pixels' img / gt values
+        float i1[4][2], i2[4][2];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int y = cur.at.y0 + 4 * q + j, x = cur.at.x0 + p + 32 * h;
+                const size_t o = (y < g.H && x < g.W) ? (size_t)y * g.W + x : 0;
+                i1[j][h] = cur.img[o];
+                i2[j][h] = cur.gt[o];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SS_STAGE_IT; j++) {
+            const int i = threadIdx.x + j * 256;
+            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+            gs[0][i] = halo.get(0, j);
+            gs[1][i] = halo.get(1, j);
+            gs[2][i] = halo.get(2, j);
+        }
+        if (t + (int)gridDim.x < g.ntiles) halo.load(src, g, ss_tile(g, t + gridDim.x));
+        __syncthreads();
+        for (int r = q; r < SS_HH; r += 8) {
+            f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+            for (int k = 0; k < 11; k++) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const float* row = gs[c] + r * SS_LS + p;
+                    s[c] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[c]);
+                }
+            }
+            hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
+        }
+        __syncthreads();
+        f2 s4[4][3];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) s4[i][c] = f2{0.f, 0.f};
+#pragma unroll
+        for (int rr = 0; rr < 14; rr++) {
+            f2 v[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) v[c] = hs[c][4 * q + rr][p];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int tap = rr - i;
+                if (tap < 0 || tap > 10) continue;
+#pragma unroll
+                for (int c = 0; c < 3; c++) s4[i][c] = pk_fma(wt.w[tap], v[c], s4[i][c]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int y = cur.at.y0 + 4 * q + j;
+            if (y >= g.H) break;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int x = cur.at.x0 + p + 32 * h;
+                if (x >= g.W) continue;
+                const float raw = i1[j][h], gt = i2[j][h];
+                const float xv = clamp ? clamp01(raw) : raw;
+                const bool pass = !clamp || (raw >= 0.f && raw <= 1.f);  // torch's clamp backward
+                const float d = xv - gt;
+                const float sgn = (float)((d > 0.f) - (d < 0.f));
+                const float ssim = s4[j][0][h] + 2.f * xv * s4[j][1][h] + gt * s4[j][2][h];
+                dimg[cur.at.plane + (size_t)y * g.W + x] = pass ? gv * (k_ssim * ssim + k_l1 * sgn) : 0.f;
+            }
+        }
+    }
+}
+
 // The reference's window (utils/loss_utils.py:46-53): exp in double, stored as float32,
 // normalised in float32 (gauss / gauss.sum()).
 static SsimWeights ssim_weights()
@@ -328,6 +597,56 @@ hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const fl
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ssim_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, ssim_weights(), img1, img2, dmap, dA, dB,
                        dC, dimg1);
+    return hipGetLastError();
+}
+
+static size_t photo_tiles_per_view(int C, int H, int W)
+{
+    return (size_t)C * ((W + SS_TW - 1) / SS_TW) * ((H + SS_TH - 1) / SS_TH);
+}
+
+size_t photo_loss_workspace_bytes(int V, int C, int H, int W)
+{
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)V * photo_tiles_per_view(C, H, W) * sizeof(double2);
+}
+
+hipError_t launch_photo_loss_fwd(const PhotoViews& views, int H, int W, float lambda, bool clamp, const float* img,
+                                 float* loss, float* dA, float* dB, float* dC, void* workspace, hipStream_t s)
+{
+    const int V = views.V, C = views.C;
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
+    if ((size_t)V * C > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    SsGrid g;
+    int blocks;
+    hipError_t e = ssim_grid(V * C, H, W, &g, &blocks);
+    if (e != hipSuccess) return e;
+    const bool train = dA && dB && dC;
+    double2* partial = static_cast<double2*>(workspace);
+    hipLaunchKernelGGL(photo_loss_fwd_kernel, dim3(blocks), dim3(256), 0, s, g, views, (float)(0.01 * 0.01),
+                       (float)(0.03 * 0.03), ssim_weights(), clamp ? 1 : 0, img, train ? dA : nullptr, dB, dC, partial);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const double n = (double)C * H * W;
+    hipLaunchKernelGGL(photo_loss_reduce_kernel, dim3(V), dim3(256), 0, s, partial, (int)photo_tiles_per_view(C, H, W),
+                       1.0 / n, (double)lambda, loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_photo_loss_bwd(const PhotoViews& views, int H, int W, float lambda, bool clamp, const float* img,
+                                 const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
+                                 hipStream_t s)
+{
+    const int V = views.V, C = views.C;
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
+    if ((size_t)V * C > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    SsGrid g;
+    int blocks;
+    hipError_t e = ssim_grid(V * C, H, W, &g, &blocks);
+    if (e != hipSuccess) return e;
+    const double n = (double)C * H * W;
+    hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, views, ssim_weights(), clamp ? 1 : 0,
+                       (float)(-(double)lambda / n), (float)((1.0 - (double)lambda) / n), img, dloss, dA, dB, dC, dimg);
     return hipGetLastError();
 }
 

@@ -64,6 +64,7 @@ def _load(path=LIB_PATH):
                                       _vp]
     lib.gsr_adam_update.argtypes = [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _vp]
     lib.gsr_adam_update_multi.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]
+    lib.gsr_densification_stats.argtypes = [_i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp]
     lib.gsr_debug_sorted_keys.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
     lib.gsr_debug_depth_sort_workspace_size.argtypes = [_i]
     lib.gsr_debug_depth_sort_workspace_size.restype = _sz
@@ -647,6 +648,38 @@ def adamUpdate(param, param_grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps,
     _check(lib.gsr_adam_update(param.data_ptr(), param_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                visible.data_ptr(), float(lr), float(b1), float(b2), float(eps), int(N), int(M),
                                _stream(dev)))
+
+
+def densification_stats(viewspace_grads, radii, max_radii2D, accum, denom, visible_count=None):
+    """gsr_densification_stats: train.py's densification statistics of V views in one launch, in
+    place and without a host synchronisation.  viewspace_grads (V,P,3) float32 and radii (V,P) int32,
+    contiguous; max_radii2D (P,) contiguous; accum / denom (P,) or (P,1) float32 with any row stride
+    (columns of one (P,2) buffer, or tensors of their own); visible_count (P,) contiguous or None."""
+    _require_gpu(viewspace_grads)
+    dev = viewspace_grads.device
+    if viewspace_grads.dim() != 3 or viewspace_grads.size(2) != 3:
+        raise RuntimeError("viewspace_grads must have dimensions (views, num_points, 3)")
+    V, P = viewspace_grads.size(0), viewspace_grads.size(1)
+    if tuple(radii.shape) != (V, P) or radii.dtype != torch.int32 or radii.device != dev:
+        raise RuntimeError(f"radii must be an int32 tensor of shape {(V, P)} on {dev}")
+    if viewspace_grads.dtype != torch.float32:
+        raise RuntimeError("viewspace_grads must be float32")
+    rows = []
+    for name, t in (("xyz_gradient_accum", accum), ("denom", denom)):
+        if t.device != dev or t.dtype != torch.float32 or t.numel() != P or t.dim() not in (1, 2) or t.size(0) != P:
+            raise RuntimeError(f"{name} must be a float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
+        rows.append(max(1, t.stride(0)))
+    flat = [("max_radii2D", max_radii2D)] + ([("visible_count", visible_count)] if visible_count is not None else [])
+    for name, t in flat:
+        if t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != (P,) or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape ({P},) on {dev}")
+    if V == 0 or P == 0:
+        return
+    grads, radii = viewspace_grads.contiguous(), radii.contiguous()
+    with torch.cuda.device(dev):
+        _check(lib.gsr_densification_stats(
+            V, P, grads.data_ptr(), radii.data_ptr(), max_radii2D.data_ptr(), accum.data_ptr(), rows[0],
+            denom.data_ptr(), rows[1], visible_count.data_ptr() if visible_count is not None else None, _stream(dev)))
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

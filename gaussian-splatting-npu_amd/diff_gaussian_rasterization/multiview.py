@@ -142,6 +142,18 @@ def add_view_stats(stats, viewspace_grad, radii):
     stats["denom"][vis] += 1
 
 
+@torch.no_grad()
+def add_batch_stats(stats, viewspace_grads, radii, visible_count=None):
+    """add_view_stats for the V views of a batch, view 0 first, in ONE HIP launch
+    (gsr_densification_stats) and without the host synchronisations of add_view_stats's
+    boolean-mask indexing.  viewspace_grads (V,P,3): the views' means2D.grad; radii (V,P) int32.
+    visible_count: an optional float32 (P,) array that also gets +1 per view that sees the
+    Gaussian.  GPU tensors only; add_view_stats remains the CPU form."""
+    from . import _C
+    _C.densification_stats(viewspace_grads, radii, stats["max_radii2D"], stats["xyz_gradient_accum"],
+                           stats["denom"], visible_count)
+
+
 def allreduce_densification_stats(stats, group=None):
     """SUM of (xyz_gradient_accum, denom) in one collective on their shared (P,2) buffer, MAX of
     max_radii2D in a second: afterwards every replica holds the statistics of all
@@ -306,12 +318,21 @@ class DataParallelTrainer:
     samples come from a generator seeded identically everywhere).  `iteration()` is train.py's
     loop body with that gating, the learning-rate schedule and the optimizer step.
     Backend-agnostic: RCCL ("nccl") on MI355X nodes, gloo in the tests.
+
+    `fused_tail=True` (opt-in; the default keeps the torch chain and its bits): the L1 + D-SSIM
+    part of the loss of all of a rank's views, with its clamp, is ONE fused_ssim.fused_l1_ssim_loss
+    call, and the statistics of step 2 plus the visibility counts ONE add_batch_stats launch
+    without host synchronisations.  Exposure and the inverse-depth term stay in torch; a batch
+    with an alpha-mask view takes the torch loss (the mask follows the clamp).
     """
 
     def __init__(self, raw, lr=None, optimizer="sparse_adam", lambda_dssim=0.2, bg=None, group=None, batched=True,
-                 seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4):
+                 seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False):
         import diff_gaussian_rasterization as dgr
         self._dgr = dgr
+        # the L1 + D-SSIM loss of a rank's views as one fused_l1_ssim_loss call and the
+        # densification statistics as one add_batch_stats launch (off: the torch chain per view)
+        self.fused_tail = fused_tail
         # > 1 (sparse Adam, several ranks): the gradient all-reduce and the optimizer step pipelined
         # over this many Gaussian ranges (reduce_and_step) in iterations without densification
         self.pipeline_chunks = pipeline_chunks
@@ -402,16 +423,17 @@ class DataParallelTrainer:
         e = self.exposures[cam_index]
         return torch.matmul(img.permute(1, 2, 0), e[:3, :3]).permute(2, 0, 1) + e[:3, 3, None, None]
 
-    def render(self, settings, act=None, cam_index=None):
+    def render(self, settings, act=None, cam_index=None, clamp=True):
         """gaussian_renderer.render with separate_sh=True: (clamped image, screen-space points, radii,
-        inverse depth)."""
+        inverse depth).  clamp=False: the exposed image before the clamp."""
         act = act or self.activations()
         means2D = torch.zeros_like(act["means3D"], requires_grad=True)
         means2D.retain_grad()
         img, radii, inv = self._dgr.GaussianRasterizer(settings)(
             means3D=act["means3D"], means2D=means2D, dc=act["dc"], shs=act["shs"], colors_precomp=None,
             opacities=act["opacities"], scales=act["scales"], rotations=act["rotations"], cov3D_precomp=None)
-        return self._expose(img, cam_index).clamp(0, 1), means2D, radii, inv
+        img = self._expose(img, cam_index)
+        return (img.clamp(0, 1) if clamp else img), means2D, radii, inv
 
     def render_views(self, settings_list, act=None):
         """render() for a batch of views in one MultiViewRasterizer call: (images (V,3,H,W) before
@@ -434,11 +456,41 @@ class DataParallelTrainer:
             img = img * extra["alpha_mask"]
         l1 = (img - gt).abs().mean()
         loss = (1.0 - self.lambda_dssim) * l1 + self.lambda_dssim * (1.0 - fused_ssim(img[None], gt[None]))
+        return self._add_depth_loss(loss, inv, extra, depth_weight)
+
+    @staticmethod
+    def _add_depth_loss(loss, inv, extra, depth_weight):
+        """train.py:128-141: the inverse-depth L1 term of a view with a depth target."""
         if depth_weight > 0 and extra.get("invdepth") is not None:
             mask = extra.get("depth_mask")
             d = (inv - extra["invdepth"]) if mask is None else (inv - extra["invdepth"]) * mask
             loss = loss + depth_weight * d.abs().mean()
         return loss
+
+    def _fused_losses(self, imgs, invs, views, depth_weight, exposed=False):
+        """_view_loss of every view, the L1 + D-SSIM part (with its clamp) as ONE
+        fused_l1_ssim_loss call; None for a batch with an alpha mask (the mask follows the
+        clamp, which the fused loss applies itself).  imgs (V,3,H,W) before the clamp and, unless
+        `exposed`, before the exposure."""
+        from fused_ssim import fused_l1_ssim_loss
+        extras = [v[2] if len(v) > 2 and v[2] is not None else {} for v in views]
+        if any(e.get("alpha_mask") is not None for e in extras):
+            return None
+        if not exposed and self.exposures is not None and any(e.get("cam") is not None for e in extras):
+            imgs = torch.stack([self._expose(imgs[j], e.get("cam")) for j, e in enumerate(extras)])
+        photo = fused_l1_ssim_loss(imgs, [v[1] for v in views], self.lambda_dssim, clamp=True)
+        return [self._add_depth_loss(photo[j], invs[j], e, depth_weight) for j, e in enumerate(extras)]
+
+    def _track(self, means2D_grads, radii, track_stats):
+        """The densification statistics and the visibility counts of V views: (V,P,3), (V,P)."""
+        with torch.no_grad():
+            if self.fused_tail and track_stats:
+                add_batch_stats(self.stats, means2D_grads, radii, self.visible_count)
+                return
+            for j in range(radii.shape[0]):
+                if track_stats:
+                    add_view_stats(self.stats, means2D_grads[j], radii[j])
+                self.visible_count += (radii[j] > 0).to(self.visible_count.dtype)
 
     def render_and_backward(self, views, depth_weight=0.0, track_stats=True):
         """Step 1-2 for this rank's views: [(GaussianRasterizationSettings, gt image (3,H,W)[, extras])]
@@ -454,27 +506,30 @@ class DataParallelTrainer:
         if self.batched and len(views) > 1:
             with self._dgr.accumulate_grads_in_place():
                 imgs, means2D, radii, invs = self.render_views([v[0] for v in views])
-            losses = [self._view_loss(self._expose(imgs[j], cam_of(v)).clamp(0, 1), invs[j], v, depth_weight)
-                      for j, v in enumerate(views)]
+            losses = self._fused_losses(imgs, invs, views, depth_weight) if self.fused_tail else None
+            if losses is None:
+                losses = [self._view_loss(self._expose(imgs[j], cam_of(v)).clamp(0, 1), invs[j], v, depth_weight)
+                          for j, v in enumerate(views)]
             torch.stack(losses).sum().backward()
-            with torch.no_grad():
-                for j in range(len(views)):
-                    if track_stats:
-                        add_view_stats(self.stats, means2D.grad[j], radii[j])
-                    self.visible_count += (radii[j] > 0).to(self.visible_count.dtype)
+            self._track(means2D.grad, radii, track_stats)
             return [l.detach() for l in losses]
         losses = []
         for v in views:
             # xyz, f_dc, f_rest enter the rasterizer as leaves whose .grad are views of the flat
             # buffer: the backward kernel adds into them directly (no separate accumulation pass)
             with self._dgr.accumulate_grads_in_place():
-                img, means2D, radii, inv = self.render(v[0], cam_index=cam_of(v))
-            loss = self._view_loss(img, inv, v, depth_weight)
+                img, means2D, radii, inv = self.render(v[0], cam_index=cam_of(v), clamp=not self.fused_tail)
+            loss = None
+            if self.fused_tail:  # img: exposed, not yet clamped
+                fused = self._fused_losses(img[None], inv[None], [v], depth_weight, exposed=True)
+                if fused is None:  # an alpha mask: the torch chain on the clamped image
+                    img = img.clamp(0, 1)
+                else:
+                    loss = fused[0]
+            if loss is None:
+                loss = self._view_loss(img, inv, v, depth_weight)
             loss.backward()
-            with torch.no_grad():
-                if track_stats:
-                    add_view_stats(self.stats, means2D.grad, radii)
-                self.visible_count += (radii > 0).to(self.visible_count.dtype)
+            self._track(means2D.grad[None], radii[None], track_stats)
             losses.append(loss.detach())
         return losses
 

@@ -4,6 +4,10 @@ train.py:31-35 imports `from fused_ssim import fused_ssim` and uses it at train.
 fused_ssim(img1, img2, padding="same", train=True) -> mean SSIM, differentiable w.r.t. img1,
 with the semantics of the reference's PyTorch ssim (utils/loss_utils.py:56-86).  The map and its
 gradient are computed by the HIP kernels behind include/fused_ssim.h; there is no CPU path.
+
+fused_l1_ssim_loss(img, gt, lambda_dssim=0.2, clamp=False) -> the whole photometric loss of
+train.py:119-124, (1 - lambda) L1 + lambda (1 - SSIM), for one image or a batch of views in one
+forward and one backward kernel (not part of the reference's module: an opt-in extra).
 """
 import ctypes
 
@@ -92,3 +96,100 @@ def fused_ssim(img1, img2, padding="same", train=True):
     img1 = img1.contiguous()
     ssim_map = FusedSSIMMap.apply(C1, C2, img1, img2, padding, train)
     return ssim_map.mean()
+
+
+# ---- the whole photometric loss of a batch of views in two kernels -------------------------------
+MAX_VIEWS = 16
+_sz = ctypes.c_size_t
+_lib.gsr_photo_loss_workspace_size.restype = _sz
+_lib.gsr_photo_loss_workspace_size.argtypes = [_i, _i, _i, _i]
+_lib.gsr_photo_loss_forward.restype = _i
+_lib.gsr_photo_loss_forward.argtypes = [_i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+_lib.gsr_photo_loss_backward.restype = _i
+_lib.gsr_photo_loss_backward.argtypes = [_i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+
+
+def _gt_pointers(gts):
+    return (_vp * len(gts))(*[g.data_ptr() for g in gts])
+
+
+class FusedL1SSIMLoss(torch.autograd.Function):
+    """(V,) losses of a contiguous float32 (V,C,H,W) batch against V separate (C,H,W) ground truths.
+    `train`: keep the partial planes for a backward."""
+
+    @staticmethod
+    def forward(ctx, img, lambda_dssim, clamp, train, *gts):
+        V, C, H, W = img.shape
+        dev = img.device
+        x = img.detach()
+        loss = torch.empty((V,), dtype=torch.float32, device=dev)
+        parts = [torch.empty_like(x) for _ in range(3)] if train else [None] * 3
+        with torch.cuda.device(dev):
+            ws = torch.empty((_lib.gsr_photo_loss_workspace_size(V, C, H, W),), dtype=torch.uint8, device=dev)
+            _gsr._check(_lib.gsr_photo_loss_forward(
+                V, C, H, W, lambda_dssim, int(clamp), x.data_ptr(), _gt_pointers(gts), loss.data_ptr(),
+                *[p.data_ptr() if train else None for p in parts], ws.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream))
+        if train:
+            ctx.save_for_backward(x, *parts, *gts)
+        ctx.lambda_dssim, ctx.clamp, ctx.train = lambda_dssim, clamp, train
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        if not ctx.train:
+            raise RuntimeError("fused_l1_ssim_loss kept no state for a backward pass")
+        x, dA, dB, dC, *gts = ctx.saved_tensors
+        V, C, H, W = x.shape
+        dev = x.device
+        g = dloss.detach().to(torch.float32).contiguous()  # stays on the device: the kernel reads it
+        grad = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            _gsr._check(_lib.gsr_photo_loss_backward(
+                V, C, H, W, ctx.lambda_dssim, int(ctx.clamp), x.data_ptr(), _gt_pointers(gts), g.data_ptr(),
+                dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), grad.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream))
+        return (grad, None, None, None) + (None,) * len(gts)
+
+
+def fused_l1_ssim_loss(img, gt, lambda_dssim=0.2, clamp=False):
+    """train.py:119-124 for a batch of views in two HIP kernels (one forward, one backward):
+
+        loss_v = (1 - lambda_dssim) mean|x_v - gt_v| + lambda_dssim (1 - mean SSIM(x_v, gt_v)),
+
+    x = img, or clamp(img, 0, 1) with `clamp`; the means run over the view's C*H*W elements and
+    SSIM is fused_ssim's (padding "same").  img: float32 (V,C,H,W) with 1 <= V <= 16, or (C,H,W);
+    gt: a tensor of the same shape, or a sequence of V (C,H,W) tensors (they are not stacked).
+    Returns the (V,) per-view losses (0-dim for a 3-D img), differentiable with respect to img
+    (sign(0) = 0; the clamp passes the gradient for 0 <= img <= 1).  Under torch.no_grad(), or when
+    img needs no gradient, nothing is kept for a backward.  GPU only; there is no CPU path."""
+    if img.device.type != "cuda":
+        raise RuntimeError(f"fused_l1_ssim_loss runs on the GPU only (HIP); got a tensor on {img.device}")
+    if img.dim() not in (3, 4):
+        raise RuntimeError("img must be (V, C, H, W) or (C, H, W)")
+    if img.dtype != torch.float32:
+        raise RuntimeError(f"img must be float32, got {img.dtype}")
+    single = img.dim() == 3
+    if torch.is_tensor(gt):
+        if gt.shape != img.shape:
+            raise RuntimeError("img and gt must have the same shape")
+        gts = [gt] if single else list(gt.unbind(0))
+    else:
+        gts = list(gt)
+    x = img[None] if single else img
+    V = x.shape[0]
+    if not 1 <= V <= MAX_VIEWS:
+        raise RuntimeError(f"fused_l1_ssim_loss takes 1 to {MAX_VIEWS} views, got {V}")
+    if len(gts) != V:
+        raise RuntimeError(f"{V} views but {len(gts)} ground-truth images")
+    for g in gts:
+        if not torch.is_tensor(g) or g.shape != x.shape[1:]:
+            raise RuntimeError("every ground-truth image must have the shape of one view of img")
+        if g.device != x.device or g.dtype != torch.float32:
+            raise RuntimeError(f"ground-truth images must be float32 on {x.device}")
+    if x.numel() == 0:
+        raise RuntimeError("img is empty")
+    gts = [g.detach().contiguous() for g in gts]
+    train = torch.is_grad_enabled() and x.requires_grad
+    loss = FusedL1SSIMLoss.apply(x.contiguous(), float(lambda_dssim), bool(clamp), train, *gts)
+    return loss[0] if single else loss

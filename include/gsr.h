@@ -370,6 +370,18 @@ int gsr_adam_update_multi(int n_groups, float* const* params, const float* const
                           const float* lrs, const float* epss, const bool* visible, float b1,
                           float b2, int N, gsr_stream_t stream);
 
+/* train.py's densification statistics (train.py:166, gaussian_model.py:471-473) for V views of
+ * the same P Gaussians in one launch, without a host synchronisation.  For every Gaussian i and
+ * v = 0 .. V-1 in order, where radii[v*P + i] > 0:
+ *   max_radii2D[i] = max(max_radii2D[i], (float)radii[v*P + i]);
+ *   accum[i*accum_stride] += sqrt(gx^2 + gy^2), (gx, gy) = viewspace_grads[(v*P + i)*3 + 0..1];
+ *   denom[i*denom_stride] += 1;  visible_count[i] += 1 (when visible_count is not NULL).
+ * The strides count floats and are >= 1 (accum and denom may be columns of one (P,2) buffer).
+ * Gaussians no view sees are not written. */
+int gsr_densification_stats(int V, int P, const float* viewspace_grads, const int* radii, float* max_radii2D,
+                            float* accum, long accum_stride, float* denom, long denom_stride,
+                            float* visible_count, gsr_stream_t stream);
+
 /* Where the forward's binning prefix (preprocess .. tile order) runs.  on = 1: on an internal
  * stream of the highest priority, forked from and joined back into the caller's stream, its side
  * work (record-slot scan, tile histogram, forward tile order) on a second internal stream;

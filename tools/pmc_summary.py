@@ -29,7 +29,10 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          "DepthSort": "depth_sort", "TileSort": "tile_sort", "fused_pass1_": "tile_sort", "CellSort": "distCUDA2",
          # SURVEY §8f side paths (bench.py aux leg)
          "knn_": "distCUDA2", "ssim_fwd_kernel": "ssim_fwd", "ssim_bwd_kernel": "ssim_bwd",
-         "adam_update_multi_kernel": "sparse_adam"}
+         "adam_update_multi_kernel": "sparse_adam",
+         # the fused training tail (tools/train_tail_bench.py)
+         "photo_loss_fwd_kernel": "photo_loss_fwd", "photo_loss_reduce_kernel": "photo_loss_fwd",
+         "photo_loss_bwd_kernel": "photo_loss_bwd", "densify_stats_kernel": "densify_stats"}
 # the kernel bench.py --pmc-child launches between its warm-up and its counted steps
 MARKER = "spin_kernel"
 # operations made of several kernels (several dispatches per call)
