@@ -1567,6 +1567,88 @@ int gsr_densification_stats(int V, int P, const float* viewspace_grads, const in
     return GSR_OK;
 }
 
+// ---- densify_and_prune (densify.hip) ----
+size_t gsr_densify_workspace_size(int P) { return densify_workspace_bytes(P); }
+
+int gsr_densify_rows_per_workgroup(void) { return DENSIFY_ROWS_PER_WG; }
+
+int gsr_densify_plan(int P, const float* accum, long accum_stride, const float* denom, long denom_stride,
+                     const float* scaling, const float* opacity, float max_grad, float dense_extent,
+                     float min_opacity, float big_extent, int N, char* workspace, int* counts, gsr_stream_t stream)
+{
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (N < 1) return fail(GSR_ERR_INVALID, "N must be >= 1");
+    if (accum_stride < 1 || denom_stride < 1) return fail(GSR_ERR_INVALID, "strides must be >= 1");
+    if (!counts) return fail(GSR_ERR_INVALID, "null pointer (counts)");
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (P == 0) return GSR_OK;
+    if (!accum || !denom || !scaling || !opacity || !workspace) return fail(GSR_ERR_INVALID, "null pointer");
+    uint32_t* h;
+    int rc = pinned(MAX_VIEWS - 1, &h);
+    if (rc) return rc;
+    h += 8;  // (the words the forward does not use)
+    const DensifyPlanArgs a = {P, N, accum, denom, accum_stride, denom_stride, scaling, opacity, max_grad,
+                               dense_extent, min_opacity, big_extent, densify_split_shrink(N)};
+    for (int k = 0; k < 5; k++) h[k] = L_PENDING;  // (every count is <= P < 2^31)
+    HIP_TRY(launch_densify_plan(a, workspace, h, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int k = 0; k < 5; k++)
+        if (__atomic_load_n(&h[k], __ATOMIC_ACQUIRE) == L_PENDING)
+            return fail(GSR_ERR_HIP, "the plan did not publish its counts");
+    const uint64_t keep_orig = h[0], keep_clone = h[1], split = h[2], keep_split = h[3], clone = h[4];
+    const uint64_t after = keep_orig + keep_clone + (uint64_t)N * keep_split;
+    if (after > 0x7fffffffull) return fail(GSR_ERR_INVALID, "the new row count overflows int");
+    counts[0] = (int)clone;
+    counts[1] = (int)split;
+    // rows the final prune removes: originals that were not split, clones, and N children per parent
+    counts[2] = (int)(((uint64_t)P - split - keep_orig) + (clone - keep_clone) + (uint64_t)N * (split - keep_split));
+    counts[3] = (int)after;
+    return GSR_OK;
+}
+
+int gsr_densify_apply(int P, int P_after, int n_split, int N, int n_groups, const int* Ms, int xyz_group,
+                      int scaling_group, int rotation_group, const float* const* src, const float* const* src_m,
+                      const float* const* src_v, float* const* dst, float* const* dst_m, float* const* dst_v,
+                      const float* samples, const char* workspace, gsr_stream_t stream)
+{
+    if (P < 0 || P_after < 0 || n_split < 0 || n_groups < 0)
+        return fail(GSR_ERR_INVALID, "P, P_after, n_split and n_groups must be >= 0");
+    if (N < 1) return fail(GSR_ERR_INVALID, "N must be >= 1");
+    if (n_groups > DENSIFY_MAX_GROUPS) return fail(GSR_ERR_INVALID, "n_groups must be <= 8");
+    if (P == 0) return GSR_OK;
+    if (n_split > P) return fail(GSR_ERR_INVALID, "n_split must be <= P");
+    if (!Ms || !src || !src_m || !src_v || !dst || !dst_m || !dst_v || !workspace)
+        return fail(GSR_ERR_INVALID, "null pointer");
+    const int roles[3] = {xyz_group, scaling_group, rotation_group};
+    const int role_M[3] = {3, 3, 4};
+    const char* role_err[3] = {"xyz_group outside [0, n_groups)", "scaling_group outside [0, n_groups)",
+                               "rotation_group outside [0, n_groups)"};
+    const char* m_err[3] = {"the xyz group must have 3 floats per row", "the scaling group must have 3 floats per row",
+                            "the rotation group must have 4 floats per row"};
+    for (int k = 0; k < 3; k++) {
+        if (roles[k] < 0 || roles[k] >= n_groups) return fail(GSR_ERR_INVALID, role_err[k]);
+        if (Ms[roles[k]] != role_M[k]) return fail(GSR_ERR_INVALID, m_err[k]);
+    }
+    if (n_split > 0 && !samples) return fail(GSR_ERR_INVALID, "null samples with n_split > 0");
+    DensifyApplyArgs a = {};
+    a.P = P; a.P_after = P_after; a.n_split = n_split; a.N = N; a.n_groups = n_groups;
+    a.xyz_group = xyz_group; a.scaling_group = scaling_group; a.rotation_group = rotation_group;
+    a.samples = samples;
+    a.shrink = densify_split_shrink(N);
+    for (int g = 0; g < n_groups; g++) {
+        if (Ms[g] < 0) return fail(GSR_ERR_INVALID, "M must be >= 0");
+        const bool moments = dst_m[g] || dst_v[g];
+        if (Ms[g] > 0 && (!src[g] || (P_after > 0 && !dst[g]))) return fail(GSR_ERR_INVALID, "null group pointer");
+        if (Ms[g] > 0 && moments && (!src_m[g] || !src_v[g] || !dst_m[g] || !dst_v[g]))
+            return fail(GSR_ERR_INVALID, "null moment pointer (a group has all four or none)");
+        a.M[g] = Ms[g];
+        a.src[g] = src[g]; a.src_m[g] = src_m[g]; a.src_v[g] = src_v[g];
+        a.dst[g] = dst[g]; a.dst_m[g] = moments ? dst_m[g] : nullptr; a.dst_v[g] = moments ? dst_v[g] : nullptr;
+    }
+    HIP_TRY(launch_densify_apply(a, workspace, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 // ---- simple_knn.h ----
 size_t gsr_knn_workspace_size(int P) { return knn_workspace_bytes(P); }
 

@@ -371,6 +371,43 @@ struct DensifyStatsArgs {
 };
 hipError_t launch_densify_stats(const DensifyStatsArgs& a, hipStream_t s);
 
+// densify_and_prune (densify.hip): the plan decides every source row's fate (one wave scans
+// DENSIFY_ROWS_PER_WAVE rows, four waves per workgroup) and leaves, in `workspace`, the source rows of
+// the output rows in output order; the apply writes every output element of every group once.
+constexpr int DENSIFY_ROWS_PER_WAVE = 1024;
+constexpr int DENSIFY_ROWS_PER_WG = 4 * DENSIFY_ROWS_PER_WAVE;
+constexpr int DENSIFY_MAX_GROUPS = 8;
+struct DensifyPlanArgs {
+    int P, N;
+    const float* accum;
+    const float* denom;
+    long accum_stride, denom_stride;
+    const float* scaling;  // (P,3) log scales
+    const float* opacity;  // (P,) logits
+    float max_grad, dense_extent, min_opacity;
+    float big_extent;  // < 0: no world-size test
+    float shrink;      // densify_split_shrink(N)
+};
+struct DensifyApplyArgs {
+    int P, P_after, n_split, N, n_groups;
+    int M[DENSIFY_MAX_GROUPS];  // floats per row
+    int xyz_group, scaling_group, rotation_group;
+    const float* src[DENSIFY_MAX_GROUPS];
+    const float* src_m[DENSIFY_MAX_GROUPS];
+    const float* src_v[DENSIFY_MAX_GROUPS];
+    float* dst[DENSIFY_MAX_GROUPS];
+    float* dst_m[DENSIFY_MAX_GROUPS];  // null: the group has no moments
+    float* dst_v[DENSIFY_MAX_GROUPS];
+    const float* samples;  // (N * n_split, 3)
+    float shrink;
+};
+size_t densify_workspace_bytes(int P);
+float densify_split_shrink(int N);  // a child's scale is its parent's divided by this (0.8 N)
+// host_counts: 5 words of pinned host memory (kept originals, kept clones, split-selected, kept split
+// parents, clone-selected), valid once the stream has been synchronised
+hipError_t launch_densify_plan(const DensifyPlanArgs& a, char* workspace, uint32_t* host_counts, hipStream_t s);
+hipError_t launch_densify_apply(const DensifyApplyArgs& a, const char* workspace, hipStream_t s);
+
 // distCUDA2 (knn.hip); host_bounds: 6 words of pinned host memory
 size_t knn_workspace_bytes(int P);
 hipError_t knn_dist2(int P, const float* pts, float* dist2, char* workspace, uint32_t* host_bounds, hipStream_t s);

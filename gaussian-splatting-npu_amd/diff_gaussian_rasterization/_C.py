@@ -65,6 +65,13 @@ def _load(path=LIB_PATH):
     lib.gsr_adam_update.argtypes = [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _vp]
     lib.gsr_adam_update_multi.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]
     lib.gsr_densification_stats.argtypes = [_i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp]
+    lib.gsr_densify_workspace_size.argtypes = [_i]
+    lib.gsr_densify_workspace_size.restype = _sz
+    lib.gsr_densify_rows_per_workgroup.argtypes = []
+    lib.gsr_densify_plan.argtypes = [_i, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _f, _f, _f, _f, _i, _vp,
+                                     ctypes.POINTER(_i), _vp]
+    lib.gsr_densify_apply.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_i), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]
     lib.gsr_debug_sorted_keys.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
     lib.gsr_debug_depth_sort_workspace_size.argtypes = [_i]
     lib.gsr_debug_depth_sort_workspace_size.restype = _sz
@@ -680,6 +687,87 @@ def densification_stats(viewspace_grads, radii, max_radii2D, accum, denom, visib
         _check(lib.gsr_densification_stats(
             V, P, grads.data_ptr(), radii.data_ptr(), max_radii2D.data_ptr(), accum.data_ptr(), rows[0],
             denom.data_ptr(), rows[1], visible_count.data_ptr() if visible_count is not None else None, _stream(dev)))
+
+
+def densify_rows_per_workgroup():
+    """Source rows one workgroup of densify_plan's scan covers (tests size their inputs from it)."""
+    return int(lib.gsr_densify_rows_per_workgroup())
+
+
+def densify_plan(accum, denom, scaling, opacity, max_grad, dense_extent, min_opacity, big_extent, N):
+    """gsr_densify_plan: decides what GaussianModel.densify_and_prune does with each of the P Gaussians.
+    accum / denom (P,) or (P,1) float32 with any row stride (as densification_stats takes them);
+    scaling (P,3) and opacity (P,1) or (P,), contiguous float32; big_extent None: no world-size test.
+    Returns (workspace, counts): the device workspace densify_apply reads, and the dict
+    {"cloned", "split", "pruned", "P_after"}.  One stream synchronisation."""
+    _require_gpu(scaling)
+    dev = scaling.device
+    if scaling.dim() != 2 or scaling.size(1) != 3 or scaling.dtype != torch.float32 or not scaling.is_contiguous():
+        raise RuntimeError("scaling must be a contiguous float32 tensor of shape (num_points, 3)")
+    P = scaling.size(0)
+    if (opacity.device != dev or opacity.dtype != torch.float32 or opacity.numel() != P or opacity.dim() not in (1, 2)
+            or opacity.size(0) != P or not opacity.is_contiguous()):
+        raise RuntimeError(f"opacity must be a contiguous float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
+    rows = []
+    for name, t in (("xyz_gradient_accum", accum), ("denom", denom)):
+        if t.device != dev or t.dtype != torch.float32 or t.numel() != P or t.dim() not in (1, 2) or t.size(0) != P:
+            raise RuntimeError(f"{name} must be a float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
+        rows.append(max(1, t.stride(0)))
+    if int(N) < 1:
+        raise RuntimeError("N must be >= 1")
+    counts = (_i * 4)()
+    workspace = torch.empty((int(lib.gsr_densify_workspace_size(P)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.gsr_densify_plan(
+            P, accum.data_ptr(), rows[0], denom.data_ptr(), rows[1], scaling.data_ptr(), opacity.data_ptr(),
+            float(max_grad), float(dense_extent), float(min_opacity), -1.0 if big_extent is None else float(big_extent),
+            int(N), workspace.data_ptr(), counts, _stream(dev)))
+    return workspace, {"cloned": counts[0], "split": counts[1], "pruned": counts[2], "P_after": counts[3]}
+
+
+def densify_apply(workspace, counts, N, names, src, src_state, dst, dst_state, samples, roles=("xyz", "scaling",
+                                                                                                "rotation")):
+    """gsr_densify_apply: writes the tensors densify_plan planned, every group in one launch.
+    workspace, counts: densify_plan's; names: the groups; src / dst: name -> the (P, ...) input and the
+    (P_after, ...) output, contiguous float32; src_state / dst_state: name -> (exp_avg, exp_avg_sq) or
+    None for a group without optimizer state; samples: (N * split, 3) standard normal draws; roles: the
+    names of the position, log-scale and quaternion groups."""
+    P = src[names[0]].size(0) if names else 0
+    _require_gpu(src[names[0]])
+    dev = src[names[0]].device
+    P_after, n_split = int(counts["P_after"]), int(counts["split"])
+    if (samples.device != dev or samples.dtype != torch.float32 or tuple(samples.shape) != (int(N) * n_split, 3)
+            or not samples.is_contiguous()):
+        raise RuntimeError(f"samples must be a contiguous float32 tensor of shape ({int(N) * n_split}, 3) on {dev}")
+    if workspace.device != dev or workspace.dtype != torch.uint8 or \
+            workspace.numel() < int(lib.gsr_densify_workspace_size(P)):
+        raise RuntimeError(f"workspace must be densify_plan's uint8 workspace for {P} points on {dev}")
+    Ms, cols = [], [[] for _ in range(6)]
+    for k in names:
+        s, d = src[k], dst[k]
+        M = s.numel() // P if P else 0
+        ss, ds = src_state.get(k), dst_state.get(k)
+        if (ss is None) != (ds is None):
+            raise RuntimeError(f"{k}: moments must be given for both the input and the output, or for neither")
+        for name, t, rows in [(k, s, P), (f"new {k}", d, P_after)] + ([] if ss is None else [
+                (f"{k} exp_avg", ss[0], P), (f"{k} exp_avg_sq", ss[1], P), (f"new {k} exp_avg", ds[0], P_after),
+                (f"new {k} exp_avg_sq", ds[1], P_after)]):
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f"densify_apply: {name} must be a contiguous float32 tensor on {dev}")
+            if t.size(0) != rows or t.numel() != rows * M:
+                raise RuntimeError(f"densify_apply: {name} has shape {tuple(t.shape)}, expected {rows} rows of {M}")
+        Ms.append(M)
+        for col, t in zip(cols, (s, None if ss is None else ss[0], None if ss is None else ss[1], d,
+                                 None if ds is None else ds[0], None if ds is None else ds[1])):
+            col.append(t.data_ptr() if t is not None and t.numel() else None)
+    n = len(names)
+    if P == 0 or P_after == 0:
+        return
+    role_idx = [names.index(r) for r in roles]
+    with torch.cuda.device(dev):
+        _check(lib.gsr_densify_apply(
+            P, P_after, n_split, int(N), n, (_i * n)(*Ms), *role_idx, *[(_vp * n)(*c) for c in cols],
+            samples.data_ptr() if n_split else None, workspace.data_ptr(), _stream(dev)))
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

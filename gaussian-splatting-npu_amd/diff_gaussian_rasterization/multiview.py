@@ -220,6 +220,42 @@ def build_rotation(r):
     return R
 
 
+@torch.no_grad()
+def fused_densify_and_prune(T, S, stats, max_grad, min_opacity, extent, max_screen_size, percent_dense=0.01, N=2,
+                            generator=None):
+    """GaussianModel.densify_and_prune (gaussian_model.py:402-469) as two HIP calls instead of the
+    chain of torch.cat / boolean-mask selections: gsr_densify_plan decides every Gaussian's fate and
+    returns the counts, gsr_densify_apply writes every new tensor once (one launch over all groups).
+    T: name -> parameter tensor (TRAIN_GROUPS; any GaussianModel's _xyz, _features_dc, ... do);
+    S: name -> optimizer state dict of that parameter (exp_avg, exp_avg_sq, step), empty or missing
+    for a parameter without state; stats: xyz_gradient_accum and denom, (P,1) each.  The split's
+    samples are drawn as randn((N * split, 3), generator=generator) -- the draws torch.normal(zeros,
+    stds) makes, leaving the generator in the same state.  Returns (T', S', counts): new tensors, new
+    state dicts (moments of the surviving rows, zeros for the new ones, `step` carried over) and
+    {"P_before", "cloned", "split", "pruned", "P_after"}.  GPU tensors only."""
+    from . import _C
+    names = [k for k in TRAIN_GROUPS if k in T]
+    src = {k: T[k].detach().contiguous() for k in names}
+    dev = src["xyz"].device
+    P0 = src["xyz"].shape[0]
+    workspace, counts = _C.densify_plan(stats["xyz_gradient_accum"], stats["denom"], src["scaling"], src["opacity"],
+                                        max_grad, percent_dense * extent, min_opacity,
+                                        0.1 * extent if max_screen_size else None, N)
+    P1 = counts["P_after"]
+    z = torch.randn((N * counts["split"], 3), generator=generator, device=dev)
+    dst = {k: torch.empty((P1,) + tuple(src[k].shape[1:]), dtype=torch.float32, device=dev) for k in names}
+    src_state, dst_state, S1 = {}, {}, {}
+    for k in names:
+        st = S.get(k) or {}
+        S1[k] = dict(st)
+        if "exp_avg" in st:
+            src_state[k] = (st["exp_avg"].contiguous(), st["exp_avg_sq"].contiguous())
+            dst_state[k] = (torch.empty_like(dst[k]), torch.empty_like(dst[k]))
+            S1[k]["exp_avg"], S1[k]["exp_avg_sq"] = dst_state[k]
+    _C.densify_apply(workspace, counts, N, names, src, src_state, dst, dst_state, z)
+    return dst, S1, dict(counts, P_before=P0)
+
+
 def inverse_sigmoid(x):
     """utils/general_utils.py inverse_sigmoid (:18-19)."""
     return torch.log(x / (1 - x))
@@ -324,12 +360,21 @@ class DataParallelTrainer:
     call, and the statistics of step 2 plus the visibility counts ONE add_batch_stats launch
     without host synchronisations.  Exposure and the inverse-depth term stay in torch; a batch
     with an alpha-mask view takes the torch loss (the mask follows the clamp).
+
+    `fused_densify=True` (opt-in, GPU parameters; the default keeps the torch chain, its bits and
+    its use of the random generator): `densify_and_prune` is `fused_densify_and_prune` -- one plan
+    and one apply launch sequence instead of the chain of appends and mask selections.  Same
+    decisions, copied values and generator state; a split child's xyz and scaling are computed in
+    the kernel and agree with the torch chain to fp32 rounding.
     """
 
     def __init__(self, raw, lr=None, optimizer="sparse_adam", lambda_dssim=0.2, bg=None, group=None, batched=True,
-                 seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False):
+                 seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False,
+                 fused_densify=False):
         import diff_gaussian_rasterization as dgr
         self._dgr = dgr
+        # densify_and_prune as the two HIP calls of fused_densify_and_prune (off: the torch chain)
+        self.fused_densify = fused_densify
         # the L1 + D-SSIM loss of a rank's views as one fused_l1_ssim_loss call and the
         # densification statistics as one add_batch_stats launch (off: the torch chain per view)
         self.fused_tail = fused_tail
@@ -698,6 +743,13 @@ class DataParallelTrainer:
         Rebuilds buffers, parameters and optimizer state for the new P; returns the counts."""
         pd = self.opt.percent_dense
         st = stats if stats is not None else self.reduced_densification_stats()
+        if self.fused_densify and self.device.type == "cuda":
+            T, S = self._tensors_and_states()
+            T, S, counts = fused_densify_and_prune(T, S, st, max_grad, min_opacity, extent, max_screen_size, pd, N,
+                                                   self.gen)
+            self._install(T, S)
+            self._skip_step = set(TRAIN_GROUPS)
+            return {k: counts[k] for k in ("P_before", "cloned", "split", "pruned", "P_after")}
         grads = st["xyz_gradient_accum"] / st["denom"]
         grads[grads.isnan()] = 0.0
         T, S = self._tensors_and_states()

@@ -382,6 +382,58 @@ int gsr_densification_stats(int V, int P, const float* viewspace_grads, const in
                             float* accum, long accum_stride, float* denom, long denom_stride,
                             float* visible_count, gsr_stream_t stream);
 
+/* GaussianModel.densify_and_prune (gaussian_model.py:402-469) in two calls: gsr_densify_plan decides
+ * what becomes of each of the P Gaussians and returns the counts the caller needs to allocate the new
+ * tensors and to draw the split's samples; gsr_densify_apply writes the new tensors.  For source row i:
+ *   g     = accum[i*accum_stride] / denom[i*denom_stride], 0 where that is NaN;
+ *   smax  = max_k expf(scaling[3i+k]);
+ *   clone = g >= max_grad && smax <= dense_extent;    split = g >= max_grad && smax > dense_extent;
+ *   low   = 1/(1 + expf(-opacity[i])) < min_opacity;
+ *   big   = big_extent >= 0 && smax > big_extent;
+ *   bigchild = big_extent >= 0 && max_k expf(logf(expf(scaling[3i+k]) / (0.8 N))) > big_extent.
+ * (The reference's screen-size test never fires -- max_radii2D is zeroed before it is read -- and is
+ * not part of this.)  Output rows, each run in source order: the rows with !split && !(low || big);
+ * the clones of the rows with clone && !(low || big); then, for r = 0 .. N-1, child r of every row with
+ * split && !(low || bigchild).  Child r of row i, the j-th of ALL split rows (pruned ones included), has
+ *   xyz     = R(rotation_i / |rotation_i|) (expf(scaling_i) * z) + xyz_i,  z = samples[3 (r n_split + j) ..],
+ *   scaling = logf(expf(scaling_i) / (0.8 N)),
+ * (R: the rotation matrix of a wxyz quaternion) and row i's values in every other group.  Adam
+ * moments are copied for the surviving rows and zero for clones and children.
+ *
+ * gsr_densify_workspace_size: bytes of device memory both calls need for P Gaussians (0 for P <= 0).
+ * gsr_densify_rows_per_workgroup: source rows one workgroup of the plan's scan covers. */
+size_t gsr_densify_workspace_size(int P);
+int gsr_densify_rows_per_workgroup(void);
+
+/* The plan.  accum, denom: device, read with element strides >= 1 (columns of one (P,2) buffer, or
+ * arrays of their own); scaling (P,3) log scales and opacity (P) logits: device, contiguous.
+ * max_grad, dense_extent (percent_dense x scene extent), min_opacity: the thresholds above;
+ * big_extent: the world-size threshold (0.1 x extent), or < 0 for none; N >= 1: children per split
+ * row.  workspace: gsr_densify_workspace_size(P) bytes of device memory, 256-byte aligned, kept
+ * unchanged until gsr_densify_apply has run.  counts: FOUR host ints, written before the call
+ * returns: the rows with clone, the rows with split (= n_split), the rows the final prune removes
+ * (a pruned split row counts N times, a pruned cloned row twice) and the new row count P_after.
+ * Synchronises `stream` once.  P == 0: counts are zero, nothing is launched. */
+int gsr_densify_plan(int P, const float* accum, long accum_stride, const float* denom, long denom_stride,
+                     const float* scaling, const float* opacity, float max_grad, float dense_extent,
+                     float min_opacity, float big_extent, int N, char* workspace, int* counts,
+                     gsr_stream_t stream);
+
+/* The apply, after gsr_densify_plan with the same P, N and workspace on the same stream; P_after and
+ * n_split are that call's counts[3] and counts[1] (when they do not match the plan in the workspace,
+ * nothing is written).  n_groups <= 8 parameter tensors of Ms[g] floats per row; xyz_group,
+ * scaling_group, rotation_group: which of them are the positions (3 floats), log scales (3) and wxyz
+ * quaternions (4).  src[g]: the (P, Ms[g]) tensor; dst[g]: the (P_after, Ms[g]) tensor to write; src_m /
+ * src_v and dst_m / dst_v: the group's Adam moments likewise -- a group with dst_m[g] and dst_v[g]
+ * NULL has no moments (the six arrays themselves are never NULL).  Host arrays of device pointers,
+ * all contiguous; no output may overlap an input.  samples: (N n_split, 3) standard normal draws on the
+ * device, NULL iff n_split == 0.  P == 0 or P_after == 0: nothing is launched.  Asynchronous. */
+int gsr_densify_apply(int P, int P_after, int n_split, int N, int n_groups, const int* Ms, int xyz_group,
+                      int scaling_group, int rotation_group, const float* const* src,
+                      const float* const* src_m, const float* const* src_v, float* const* dst,
+                      float* const* dst_m, float* const* dst_v, const float* samples, const char* workspace,
+                      gsr_stream_t stream);
+
 /* Where the forward's binning prefix (preprocess .. tile order) runs.  on = 1: on an internal
  * stream of the highest priority, forked from and joined back into the caller's stream, its side
  * work (record-slot scan, tile histogram, forward tile order) on a second internal stream;

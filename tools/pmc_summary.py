@@ -32,7 +32,10 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          "adam_update_multi_kernel": "sparse_adam",
          # the fused training tail (tools/train_tail_bench.py)
          "photo_loss_fwd_kernel": "photo_loss_fwd", "photo_loss_reduce_kernel": "photo_loss_fwd",
-         "photo_loss_bwd_kernel": "photo_loss_bwd", "densify_stats_kernel": "densify_stats"}
+         "photo_loss_bwd_kernel": "photo_loss_bwd", "densify_stats_kernel": "densify_stats",
+         # densify_and_prune (multiview.fused_densify_and_prune)
+         "densify_decide_kernel": "densify_plan", "densify_offsets_kernel": "densify_plan",
+         "densify_scatter_kernel": "densify_plan", "densify_apply_kernel": "densify_apply"}
 # the kernel bench.py --pmc-child launches between its warm-up and its counted steps
 MARKER = "spin_kernel"
 # operations made of several kernels (several dispatches per call)

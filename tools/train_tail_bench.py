@@ -6,7 +6,14 @@
           (DataParallelTrainer._view_loss on the clamped image)   vs   one fused_l1_ssim_loss
           call (photo_loss_fwd_kernel + photo_loss_bwd_kernel) and its backward;
   stats:  V x multiview.add_view_stats (boolean-mask indexing, a host synchronisation each)
-          vs   one multiview.add_batch_stats launch (densify_stats_kernel).
+          vs   one multiview.add_batch_stats launch (densify_stats_kernel);
+  densify: DataParallelTrainer.densify_and_prune as the torch chain (two appends and two mask
+          selections over six tensors and their Adam moments)   vs   fused_densify=True (one
+          gsr_densify_plan and one gsr_densify_apply).  Both sides start every call from clones of the
+          same 1M-Gaussian start (made outside the timed region) and include the rebuild of the flat
+          gradient buffer both share; "fused_call" is multiview.fused_densify_and_prune alone, which
+          the GB/s figure refers to.  Thresholds are quantiles of the seed-0 data: about 5 % of the
+          rows clone, 5 % split and 5 % are pruned (the fractions are recorded).
 
 Defaults are the bench's flagship shape: 8 views, 1920x1080, 1M Gaussians, seed-0 data.  The two
 sides alternate call by call; every call is bracketed by device events and ends in a
@@ -14,7 +21,8 @@ synchronise.  `--rounds` rounds of `--reps` timed calls per side (after `--warmu
 give one median per round; reported are the median of the round medians and their spread
 (max - min).  The result -- times, spreads, the algorithmic bytes of the fused forms (11 floats per
 plane-pixel for the loss) and the two sides' agreement on these inputs -- goes to --out as JSON
-and to stdout as one line.  Without a GPU it fails.
+and to stdout as one line.  `--legs` selects the legs to run; the others keep their block of an
+existing --out file.  Without a GPU it fails.
 """
 import argparse
 import json
@@ -61,10 +69,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--legs", default="loss,stats,densify", help="comma-separated: loss, stats, densify")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_tail.json"))
     args = ap.parse_args()
     if args.warmup < 3 or args.reps < 20:
         ap.error("at least 3 warm-ups and 20 timed repetitions per side")
+    legs = set(args.legs.split(","))
+    if not legs or legs - {"loss", "stats", "densify"}:
+        ap.error("--legs takes loss, stats and densify")
 
     import torch
     if not torch.cuda.is_available():
@@ -73,6 +85,40 @@ def main():
     from fused_ssim import fused_l1_ssim_loss, fused_ssim
 
     dev = torch.device("cuda", 0)
+    V, H, W, P, lam = args.views, args.height, args.width, args.points, args.lambda_dssim
+
+    def side(r, nbytes, of="fused"):
+        out = {}
+        for k, (med, spread, rounds) in r.items():
+            out[k] = {"median_ms": med, "spread_ms": spread, "round_medians_ms": rounds}
+        out[of]["algorithmic_bytes"] = nbytes
+        out[of]["algorithmic_GBps"] = nbytes / (r[of][0] * 1e-3) / 1e9
+        noise = max(r["torch"][1], r["fused"][1])
+        out["fused_faster_beyond_spread"] = bool(r["torch"][0] - r["fused"][0] > noise)
+        out["speedup"] = r["torch"][0] / r["fused"][0]
+        return out
+
+    result = {}
+    if os.path.exists(args.out):  # legs not run now keep their blocks
+        with open(args.out) as f:
+            result = json.load(f)
+    result.update({
+        "tool": "tools/train_tail_bench.py", "device": torch.cuda.get_device_name(dev),
+        "views": V, "width": W, "height": H, "points": P, "lambda_dssim": lam, "seed": 0,
+        "warmup": args.warmup, "reps": args.reps, "rounds": args.rounds,
+        "timing": "device events around each call, synchronised; sides alternate call by call"})
+    if legs & {"loss", "stats"}:
+        loss_stats_legs(args, legs, result, side, torch, multiview, fused_l1_ssim_loss, fused_ssim, dev)
+    if "densify" in legs:
+        result["densify"] = densify_leg(args, side, torch, multiview, dev)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+
+
+def loss_stats_legs(args, legs, result, side, torch, multiview, fused_l1_ssim_loss, fused_ssim, dev):
     V, H, W, P, lam = args.views, args.height, args.width, args.points, args.lambda_dssim
     g = torch.Generator(device="cpu").manual_seed(0)
     img = (1.4 * torch.rand((V, 3, H, W), generator=g) - 0.2).to(dev).requires_grad_(True)
@@ -110,53 +156,164 @@ def main():
         multiview.add_batch_stats(stats["fused"], grads, radii, counts["fused"])
 
     # the two sides on these inputs (before any timing)
-    lt = torch.stack([l.detach() for l in torch_loss()])
-    gt_ = img.grad.clone()
-    lf = fused_loss().detach()
-    gf = img.grad.clone()
-    torch_stats()
-    fused_stats()
-    agreement = {
-        "loss_max_abs_diff": float((lt - lf).abs().max()),
-        "grad_max_abs_diff_over_max": float((gt_ - gf).abs().max() / gt_.abs().max()),
-        "stats_counts_equal": bool(torch.equal(stats["torch"]["denom"], stats["fused"]["denom"]) and
-                                   torch.equal(stats["torch"]["max_radii2D"], stats["fused"]["max_radii2D"]) and
-                                   torch.equal(counts["torch"], counts["fused"])),
-        "accum_max_rel_diff": float(((stats["torch"]["xyz_gradient_accum"] - stats["fused"]["xyz_gradient_accum"]).abs()
-                                     / stats["torch"]["xyz_gradient_accum"].abs().clamp_min(1e-30)).max()),
-    }
-    del gt_, gf
-
-    loss = alternate({"torch": torch_loss, "fused": fused_loss}, args.warmup, args.reps, args.rounds, torch)
-    stat = alternate({"torch": torch_stats, "fused": fused_stats}, args.warmup, args.reps, args.rounds, torch)
-
-    def side(r, nbytes):
-        out = {}
-        for k, (med, spread, rounds) in r.items():
-            out[k] = {"median_ms": med, "spread_ms": spread, "round_medians_ms": rounds}
-        out["fused"]["algorithmic_bytes"] = nbytes
-        out["fused"]["algorithmic_GBps"] = nbytes / (r["fused"][0] * 1e-3) / 1e9
-        noise = max(r["torch"][1], r["fused"][1])
-        out["fused_faster_beyond_spread"] = bool(r["torch"][0] - r["fused"][0] > noise)
-        out["speedup"] = r["torch"][0] / r["fused"][0]
-        return out
-
-    result = {
-        "tool": "tools/train_tail_bench.py", "device": torch.cuda.get_device_name(dev),
-        "views": V, "width": W, "height": H, "points": P, "lambda_dssim": lam, "seed": 0,
-        "warmup": args.warmup, "reps": args.reps, "rounds": args.rounds,
-        "timing": "device events around each call, synchronised; sides alternate call by call",
+    agreement = result.setdefault("agreement", {})
+    if "loss" in legs:
+        lt = torch.stack([l.detach() for l in torch_loss()])
+        gt_ = img.grad.clone()
+        lf = fused_loss().detach()
+        gf = img.grad.clone()
+        agreement["loss_max_abs_diff"] = float((lt - lf).abs().max())
+        agreement["grad_max_abs_diff_over_max"] = float((gt_ - gf).abs().max() / gt_.abs().max())
+        del gt_, gf
+        loss = alternate({"torch": torch_loss, "fused": fused_loss}, args.warmup, args.reps, args.rounds, torch)
         # forward: img, gt in, 3 partial planes out; backward: 3 planes, img, gt in, dL/dimg out
-        "loss": side(loss, 11 * 4 * V * 3 * H * W),
+        result["loss"] = side(loss, 11 * 4 * V * 3 * H * W)
+    if "stats" in legs:
+        torch_stats()
+        fused_stats()
+        agreement["stats_counts_equal"] = bool(
+            torch.equal(stats["torch"]["denom"], stats["fused"]["denom"]) and
+            torch.equal(stats["torch"]["max_radii2D"], stats["fused"]["max_radii2D"]) and
+            torch.equal(counts["torch"], counts["fused"]))
+        agreement["accum_max_rel_diff"] = float(
+            ((stats["torch"]["xyz_gradient_accum"] - stats["fused"]["xyz_gradient_accum"]).abs()
+             / stats["torch"]["xyz_gradient_accum"].abs().clamp_min(1e-30)).max())
+        stat = alternate({"torch": torch_stats, "fused": fused_stats}, args.warmup, args.reps, args.rounds, torch)
         # radii and (gx, gy) of every (view, Gaussian); accum, denom, max radius and count read and written
-        "stats": side(stat, V * P * 12 + P * 32),
-        "agreement": agreement,
+        result["stats"] = side(stat, V * P * 12 + P * 32)
+
+
+def densify_leg(args, side, torch, multiview, dev):
+    """The torch densify_and_prune against the fused one (see the module docstring)."""
+    P, N, pd = args.points, 2, 0.01
+    names = multiview.TRAIN_GROUPS
+    g = torch.Generator(device="cpu").manual_seed(0)
+    start = {"xyz": torch.randn((P, 3), generator=g), "f_dc": torch.randn((P, 1, 3), generator=g),
+             "f_rest": 0.1 * torch.randn((P, 15, 3), generator=g), "opacity": 2.0 * torch.randn((P, 1), generator=g),
+             "scaling": torch.log(0.003 + 0.02 * torch.rand((P, 3), generator=g)),
+             "rotation": torch.randn((P, 4), generator=g)}
+    start = {k: v.to(dev) for k, v in start.items()}
+    moments = {k: (torch.randn(v.shape, generator=g).to(dev), torch.rand(v.shape, generator=g).to(dev))
+               for k, v in start.items()}
+    stats = multiview.densification_stats(P, dev)
+    stats["xyz_gradient_accum"].copy_((2e-3 * torch.rand((P, 1), generator=g)).to(dev))
+    stats["denom"].copy_(torch.randint(1, 9, (P, 1), generator=g).float().to(dev))
+    # thresholds: the hottest 10 % of the rows, half of them small (clone) and half large (split);
+    # the 5 % most transparent rows are pruned.  No world-size test (max_screen_size None).
+    grad = (stats["xyz_gradient_accum"] / stats["denom"]).squeeze(1)
+    smax = start["scaling"].exp().max(dim=1).values
+    sig = torch.sigmoid(start["opacity"]).squeeze(1)
+    def clear(values, thr, window=1e-6):
+        """thr raised until no value is within `window` (relative; a few fp32 ulps: torch's exp and
+        sigmoid and the kernel's may round differently) of it, so both sides decide alike."""
+        for _ in range(10000):
+            if not bool(((values.double() / thr - 1.0).abs() < window).any()):
+                break
+            thr *= 1.0 + 3.0 * window
+        return thr
+    max_grad = clear(grad, float(torch.quantile(grad[::8], 0.9)))
+    hot = grad >= max_grad
+    extent = clear(smax, float(smax[hot].median())) / pd
+    min_opacity = clear(sig, float(torch.quantile(sig[::8], 0.05)))
+    clone, split, low = hot & (smax <= pd * extent), hot & (smax > pd * extent), sig < min_opacity
+    n_ko, n_kc, n_ks = int((~split & ~low).sum()), int((clone & ~low).sum()), int((split & ~low).sum())
+    P_after = n_ko + n_kc + N * n_ks
+
+    trainers = {k: multiview.DataParallelTrainer({n: start[n][:1] for n in names}, fused_densify=(k == "fused"))
+                for k in ("torch", "fused")}
+    step = torch.tensor(1.0)
+
+    def fresh():
+        T = {n: start[n].clone() for n in names}
+        S = {n: {"step": step, "exp_avg": moments[n][0].clone(), "exp_avg_sq": moments[n][1].clone()} for n in names}
+        return T, S
+
+    def reset(k):  # outside the timed region: both sides replace their inputs
+        trainers[k]._install(*fresh())
+
+    did = {}
+
+    def run(k):
+        def fn():
+            did[k] = trainers[k].densify_and_prune(max_grad, min_opacity, extent, None, stats=stats, N=N)
+        return fn
+
+    held = {}
+
+    def fused_call():
+        T, S = held.pop("in")
+        held["out"] = multiview.fused_densify_and_prune(T, S, stats, max_grad, min_opacity, extent, None, pd, N,
+                                                        trainers["fused"].gen)
+
+    # agreement of the two sides on these inputs, from equal generator states
+    out = {}
+    for k in ("torch", "fused"):
+        trainers[k].gen.manual_seed(0)
+        reset(k)
+        run(k)()
+        tr = trainers[k]
+        out[k] = ({n: p.detach() for n, p in tr.params.items()},
+                  {n: tr.optimizer.state[p] for n, p in tr.params.items()})
+    first_child = P_after - N * n_ks
+    copied_equal = did["torch"] == did["fused"] and did["fused"]["P_after"] == P_after
+    for n in names:
+        rows = first_child if n in ("xyz", "scaling") else P_after
+        copied_equal = copied_equal and torch.equal(out["torch"][0][n][:rows], out["fused"][0][n][:rows])
+        for m in ("exp_avg", "exp_avg_sq"):
+            copied_equal = copied_equal and torch.equal(out["torch"][1][n][m], out["fused"][1][n][m])
+    agreement = {
+        "counts": did["fused"], "counts_equal": did["torch"] == did["fused"],
+        "copied_rows_and_moments_bit_equal": bool(copied_equal),
+        "generator_state_equal": bool(torch.equal(trainers["torch"].gen.get_state(),
+                                                  trainers["fused"].gen.get_state())),
+        "children_xyz_max_abs_diff": float((out["torch"][0]["xyz"][first_child:]
+                                            - out["fused"][0]["xyz"][first_child:]).abs().max()),
+        "children_scaling_max_abs_diff": float((out["torch"][0]["scaling"][first_child:]
+                                                - out["fused"][0]["scaling"][first_child:]).abs().max()),
     }
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
-    print(json.dumps(result))
+    del out
+
+    # timing: alternate() with the untimed reset before every timed call
+    def timed_after(prepare, fn):
+        def call():
+            prepare()
+            torch.cuda.synchronize()
+            return fn
+        return call
+    sides = {"torch": timed_after(lambda: reset("torch"), run("torch")),
+             "fused": timed_after(lambda: reset("fused"), run("fused")),
+             "fused_call": timed_after(lambda: held.__setitem__("in", fresh()), fused_call)}
+    r = alternate_prepared(sides, args.warmup, args.reps, args.rounds, torch)
+    # plan: 24 B in and 1 B out per row, 1 B in again, the three lists written; apply: the lists read,
+    # 236 B x (parameter + two moments) written per output row, the same read for kept originals, the
+    # parameters alone read for clones and children, 12 B of samples per child
+    lists = 4 * (n_ko + n_kc) + 8 * n_ks
+    nbytes = 26 * P + 2 * lists + 3 * 236 * P_after + 3 * 236 * n_ko + 236 * (P_after - n_ko) + 12 * N * n_ks
+    res = side(r, nbytes, of="fused_call")
+    res["fractions"] = {"cloned": float(clone.sum()) / P, "split": float(split.sum()) / P,
+                        "pruned_rows": float(low.sum()) / P}
+    res["thresholds"] = {"max_grad": max_grad, "min_opacity": min_opacity, "extent": extent, "percent_dense": pd,
+                         "N": N, "max_screen_size": None}
+    res["includes"] = ("torch and fused: densify_and_prune with the rebuild of the flat gradient buffer both share; "
+                       "fused_call: fused_densify_and_prune alone (plan, read-back, randn, allocation, apply)")
+    res["agreement"] = agreement
+    return res
+
+
+def alternate_prepared(sides, warmup, reps, rounds, torch):
+    """alternate() for sides that need untimed preparation: side() prepares and returns the call to time."""
+    for _ in range(warmup):
+        for prep in sides.values():
+            timed(prep(), torch)
+    meds = {k: [] for k in sides}
+    for _ in range(rounds):
+        t = {k: [] for k in sides}
+        for _ in range(reps):
+            for k, prep in sides.items():
+                t[k].append(timed(prep(), torch))
+        for k in sides:
+            meds[k].append(statistics.median(t[k]))
+    return {k: (statistics.median(m), max(m) - min(m), m) for k, m in meds.items()}
 
 
 if __name__ == "__main__":
