@@ -7,7 +7,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -93,106 +92,53 @@ int pinned(int slot, uint32_t** out)
 // the fork / join events order streams of one device only: no system-scope fence (the host never
 // inspects them; what the host reads -- num_rendered -- the scan stores with system-scope atomics)
 constexpr unsigned EVENT_FLAGS = hipEventDisableTiming | hipEventDisableSystemFence;
-constexpr int PREFIX_STREAMS = 4;  // views whose binning prefixes run side by side (gsr_forward_views)
+// An internal stream of the highest priority with the events that order it against the stream it is
+// forked from (in) and joined back into (out); created lazily, one per host thread and device.
 struct PrefixStream {
-    hipStream_t s[PREFIX_STREAMS] = {};
-    hipEvent_t fork = nullptr, join = nullptr;
-    // side work of a prefix (the index-order scan) beside its critical path
-    hipStream_t aux = nullptr;
-    hipEvent_t aux_in = nullptr, aux_out = nullptr;
+    hipStream_t s = nullptr;
+    hipEvent_t in = nullptr, out = nullptr;
 };
 constexpr int MAX_DEVICES = 64;
 thread_local PrefixStream g_prefix[MAX_DEVICES];
+// side work of a prefix (the index-order scan, the rects' difference array) beside its critical path
+thread_local PrefixStream g_aux[MAX_DEVICES];
 // gsr_set_prefix_stream: 0 = everything on the caller's stream; 1 = the prefix on its own
 // high-priority stream (forked from the caller's, joined before render_fwd) and its side work on
 // the auxiliary stream; 2 = the prefix on the caller's stream, its side work on the auxiliary stream
 thread_local int g_prefix_mode = 1;
 
-// n (<= PREFIX_STREAMS) prefix streams of the current device, each forked from `caller`; all of
-// them the caller's own stream when the prefix streams are off (or the device is out of range).
-int prefix_fork(hipStream_t caller, int n, hipStream_t* out)
+// *out: the current device's stream of `streams`, forked from `from` (it waits for everything
+// enqueued on `from` so far); `from` itself when the stream is off (or the device is out of range).
+int stream_fork(PrefixStream* streams, bool on, hipStream_t from, hipStream_t* out)
 {
-    for (int k = 0; k < n; k++) out[k] = caller;
-    if (g_prefix_mode != 1) return GSR_OK;
+    *out = from;
+    if (!on) return GSR_OK;
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail_hip(e, __LINE__);
+    HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= MAX_DEVICES) return GSR_OK;
-    PrefixStream& ps = g_prefix[dev];
-    if (!ps.fork) {
-        if ((e = hipEventCreateWithFlags(&ps.fork, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.join, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
-    }
-    if ((e = hipEventRecord(ps.fork, caller)) != hipSuccess) return fail_hip(e, __LINE__);
-    for (int k = 0; k < n; k++) {
-        if (!ps.s[k]) {
-            int least = 0, greatest = 0;
-            if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return fail_hip(e, __LINE__);
-            if ((e = hipStreamCreateWithPriority(&ps.s[k], hipStreamNonBlocking, greatest)) != hipSuccess)
-                return fail_hip(e, __LINE__);
-        }
-        if ((e = hipStreamWaitEvent(ps.s[k], ps.fork, 0)) != hipSuccess) return fail_hip(e, __LINE__);
-        out[k] = ps.s[k];
-    }
-    return GSR_OK;
-}
-
-int prefix_begin(hipStream_t caller, hipStream_t* out) { return prefix_fork(caller, 1, out); }
-
-int current_device()
-{
-    int dev = 0;
-    return hipGetDevice(&dev) == hipSuccess ? dev : 0;
-}
-
-// The auxiliary stream of the current device, forked from `s` (s itself when the prefix streams
-// are off); aux_join makes `s` wait for everything enqueued on it so far.
-int aux_fork(hipStream_t s, hipStream_t* out)
-{
-    *out = s;
-    if (g_prefix_mode == 0) return GSR_OK;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail_hip(e, __LINE__);
-    if (dev < 0 || dev >= MAX_DEVICES) return GSR_OK;
-    PrefixStream& ps = g_prefix[dev];
-    if (!ps.aux) {
+    PrefixStream& ps = streams[dev];
+    if (!ps.s) {
         int least = 0, greatest = 0;
-        if ((e = hipDeviceGetStreamPriorityRange(&least, &greatest)) != hipSuccess) return fail_hip(e, __LINE__);
-        if ((e = hipStreamCreateWithPriority(&ps.aux, hipStreamNonBlocking, greatest)) != hipSuccess)
-            return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.aux_in, EVENT_FLAGS)) != hipSuccess) return fail_hip(e, __LINE__);
-        if ((e = hipEventCreateWithFlags(&ps.aux_out, EVENT_FLAGS)) != hipSuccess)
-            return fail_hip(e, __LINE__);
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipEventCreateWithFlags(&ps.in, EVENT_FLAGS));
+        HIP_TRY(hipEventCreateWithFlags(&ps.out, EVENT_FLAGS));
+        HIP_TRY(hipStreamCreateWithPriority(&ps.s, hipStreamNonBlocking, greatest));
     }
-    if ((e = hipEventRecord(ps.aux_in, s)) != hipSuccess) return fail_hip(e, __LINE__);
-    if ((e = hipStreamWaitEvent(ps.aux, ps.aux_in, 0)) != hipSuccess) return fail_hip(e, __LINE__);
-    *out = ps.aux;
+    HIP_TRY(hipEventRecord(ps.in, from));
+    HIP_TRY(hipStreamWaitEvent(ps.s, ps.in, 0));
+    *out = ps.s;
     return GSR_OK;
 }
 
-int aux_join(hipStream_t s, hipStream_t aux)
+// `from` waits for everything enqueued so far on `forked`, which stream_fork(streams, ...) gave
+int stream_join(PrefixStream* streams, hipStream_t from, hipStream_t forked)
 {
-    if (aux == s) return GSR_OK;
+    if (forked == from) return GSR_OK;
     int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail_hip(e, __LINE__);
-    PrefixStream& ps = g_prefix[dev];
-    if ((e = hipEventRecord(ps.aux_out, aux)) != hipSuccess) return fail_hip(e, __LINE__);
-    if ((e = hipStreamWaitEvent(s, ps.aux_out, 0)) != hipSuccess) return fail_hip(e, __LINE__);
-    return GSR_OK;
-}
-
-// the caller's stream waits for everything enqueued on the prefix stream so far
-int prefix_end(hipStream_t caller, hipStream_t prefix)
-{
-    if (prefix == caller) return GSR_OK;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail_hip(e, __LINE__);
-    PrefixStream& ps = g_prefix[dev];
-    if ((e = hipEventRecord(ps.join, prefix)) != hipSuccess) return fail_hip(e, __LINE__);
-    if ((e = hipStreamWaitEvent(caller, ps.join, 0)) != hipSuccess) return fail_hip(e, __LINE__);
+    HIP_TRY(hipGetDevice(&dev));
+    PrefixStream& ps = streams[dev];
+    HIP_TRY(hipEventRecord(ps.out, forked));
+    HIP_TRY(hipStreamWaitEvent(from, ps.out, 0));
     return GSR_OK;
 }
 
@@ -261,6 +207,28 @@ template <typename T>
 T* at(char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
 template <typename T>
 const T* at(const char* base, size_t off) { return reinterpret_cast<const T*>(base + off); }
+
+// What the entry points' positional arguments say, filled once at the ABI boundary.
+// The Gaussians and what every view of a call shares (M as the caller counts it: without dc)
+struct Scene {
+    int P, D, M;
+    const float *means3D, *dc, *shs, *colors_precomp, *opacities, *scales;
+    float scale_modifier;
+    const float *rotations, *cov3D_precomp;
+    bool prefiltered, antialiasing;
+    int width, height;
+};
+struct Camera {
+    const float *view, *proj, *campos;
+    float tan_fovx, tan_fovy;
+};
+// One view's state buffers and outputs (radii null: the GeometryState's own)
+struct ViewState {
+    char *geometry, *image, *binning;
+    size_t binning_capacity;
+    float *out_color, *invdepth;
+    int* radii;
+};
 
 }  // namespace
 
@@ -343,30 +311,33 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 }
 
 
-// The arguments of one view's preprocess (argument checks; the view's pinned read-back slot is
-// reset: *h_out its host words, *hdev_out their device address).
-static int forward_geometry_args(char* geometry_buffer, char* image_buffer, int P, int D, int M, int width,
-                                 int height, const float* means3D, const float* dc, const float* shs,
-                                 const float* colors_precomp, const float* opacities, const float* scales,
-                                 float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                 const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                                 float tan_fovx, float tan_fovy, bool prefiltered, bool antialiasing, int* radii,
-                                 int slot, PreprocessArgs* out, uint32_t** h_out, uint32_t** hdev_out)
+// The forward's argument checks for one view (no HIP call)
+static int forward_args_check(const Scene& sc, const ViewState& vs)
 {
-    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID, "image size must be positive");
-    if (!colors_precomp && !dc && (!shs || M <= 0))
+    if (sc.width <= 0 || sc.height <= 0) return fail(GSR_ERR_INVALID, "image size must be positive");
+    if (!sc.colors_precomp && !sc.dc && (!sc.shs || sc.M <= 0))
         return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M < 0) return fail(GSR_ERR_INVALID, "M (rest SH coefficients) must be >= 0");
-    if (dc && colors_precomp)
+    if (sc.dc && sc.M < 0) return fail(GSR_ERR_INVALID, "M (rest SH coefficients) must be >= 0");
+    if (sc.dc && sc.colors_precomp)
         return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M > 0 && !shs) return fail(GSR_ERR_INVALID, "dc given with M > 0 rest coefficients but shs is NULL");
-    if (!cov3D_precomp && (!scales || !rotations))
+    if (sc.dc && sc.M > 0 && !sc.shs)
+        return fail(GSR_ERR_INVALID, "dc given with M > 0 rest coefficients but shs is NULL");
+    if (!sc.cov3D_precomp && (!sc.scales || !sc.rotations))
         return fail(GSR_ERR_INVALID,
                     "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
-    if (!geometry_buffer || !image_buffer) return fail(GSR_ERR_ALLOC, "null state buffer");
+    if (!vs.geometry || !vs.image) return fail(GSR_ERR_ALLOC, "null state buffer");
+    return GSR_OK;
+}
 
+// The arguments of one view's preprocess (checked: forward_args_check); the view's pinned read-back
+// slot is reset: *h_out its host words, *hdev_out their device address.
+// geometry_outputs: GeometryState's means2D, depths, rgb and conic_opacity are written
+static int preprocess_args(const Scene& sc, const Camera& cam, const ViewState& vs, int slot, bool geometry_outputs,
+                           PreprocessArgs* out, uint32_t** h_out, uint32_t** hdev_out)
+{
+    const int P = sc.P, width = sc.width, height = sc.height;
     const GeomLayout g = geom_layout(P);
-    char* gb = geometry_buffer;
+    char* gb = vs.geometry;
     // h[0]: prefiltered violation (written by preprocess), h[2]: num_rendered (written by the scan).
     // This thread's previous forward has read its num_rendered back, so no kernel still writes them.
     uint32_t* h;
@@ -379,23 +350,26 @@ static int forward_geometry_args(char* geometry_buffer, char* image_buffer, int 
     HIP_TRY(hipHostGetDevicePointer((void**)&h_dev, h, 0));
 
     PreprocessArgs& a = *out;
-    a.P = P; a.D = D; a.M = dc ? M + 1 : M; a.W = width; a.H = height;  // kernels count the dc coefficient
-    a.dc = dc;
-    a.means3D = means3D; a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations;
-    a.opacities = opacities; a.shs = shs; a.cov3D_precomp = cov3D_precomp; a.colors_precomp = colors_precomp;
-    a.view = viewmatrix; a.proj = projmatrix; a.campos = cam_pos;
-    a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-    a.focal_y = height / (2.0f * tan_fovy);
-    a.focal_x = width / (2.0f * tan_fovx);
+    a.P = P; a.D = sc.D; a.M = sc.dc ? sc.M + 1 : sc.M; a.W = width; a.H = height;  // kernels count the dc coefficient
+    a.dc = sc.dc;
+    a.means3D = sc.means3D; a.scales = sc.scales; a.scale_modifier = sc.scale_modifier; a.rotations = sc.rotations;
+    a.opacities = sc.opacities; a.shs = sc.shs; a.cov3D_precomp = sc.cov3D_precomp;
+    a.colors_precomp = sc.colors_precomp;
+    a.view = cam.view; a.proj = cam.proj; a.campos = cam.campos;
+    a.tan_fovx = cam.tan_fovx; a.tan_fovy = cam.tan_fovy;
+    a.focal_y = height / (2.0f * cam.tan_fovy);
+    a.focal_x = width / (2.0f * cam.tan_fovx);
     const TileGrid tg(width, height);
     a.grid_x = tg.gx;
     a.grid_y = tg.gy;
-    a.prefiltered = prefiltered; a.antialiasing = antialiasing;
-    a.radii = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
-    a.means2D = at<float>(gb, g.off[GEOM_MEANS2D]);
-    a.depths = at<float>(gb, g.off[GEOM_DEPTH]);
-    a.rgb = at<float>(gb, g.off[GEOM_RGB]);
-    a.conic_opacity = at<float>(gb, g.off[GEOM_CONIC_OPACITY]);
+    a.prefiltered = sc.prefiltered; a.antialiasing = sc.antialiasing;
+    a.radii = vs.radii ? vs.radii : at<int>(gb, g.off[GEOM_RADII]);
+    // (the batched forward leaves them out: nothing reads them after the forward -- preprocess_bwd
+    // recomputes conic_opacity -- and they are 40 B per visible Gaussian and view)
+    a.means2D = geometry_outputs ? at<float>(gb, g.off[GEOM_MEANS2D]) : nullptr;
+    a.depths = geometry_outputs ? at<float>(gb, g.off[GEOM_DEPTH]) : nullptr;
+    a.rgb = geometry_outputs ? at<float>(gb, g.off[GEOM_RGB]) : nullptr;
+    a.conic_opacity = geometry_outputs ? at<float>(gb, g.off[GEOM_CONIC_OPACITY]) : nullptr;
     a.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
     a.tiles_touched = at<uint32_t>(gb, g.off[GEOM_TILES_TOUCHED]);
     a.host_flags = h_dev;
@@ -416,7 +390,7 @@ static int forward_geometry_args(char* geometry_buffer, char* image_buffer, int 
     a.tile_diff = nullptr;
     a.tile_diff_words = 0;
     if (use_tile_diff(a.grid_x, a.grid_y)) {  // the tile ranges from the rects' difference array
-        a.tile_diff = at<int>(image_buffer, image_layout(width, height).off[IMG_TILE_DIFF]);
+        a.tile_diff = at<int>(vs.image, image_layout(width, height).off[IMG_TILE_DIFF]);
         a.tile_diff_words = (int)((a.grid_x + 1) * (a.grid_y + 1));
     }
     *h_out = h;
@@ -457,90 +431,6 @@ static SortJob depth_sort_job(char* gb, const PreprocessArgs& a, uint32_t* h_dev
     j.host_wide = h_dev + 1;
     j.gsum_zeroed = true;  // (preprocess)
     return j;
-}
-
-// After preprocess: the record-slot scan, the depth sort and the tile-count scan of one view.
-static int forward_geometry_sort(const PreprocessArgs& a, char* gb, char* ib, int width, int height, int P,
-                                 uint32_t* h_dev, hipStream_t s, bool debug, bool use_aux, SortJob* dsort_out,
-                                 ScanJob* off_out)
-{
-    const GeomLayout g = geom_layout(P);
-    // 1b. each Gaussian's first gradient-record slot: index-order exclusive scan of the tile counts
-    //     (records in Gaussian order: preprocess_bwd's per-Gaussian gathers are contiguous), on the
-    //     auxiliary stream beside the depth sort; the tile sort's first pass (which reads it) waits for it
-    hipStream_t aux = s;
-    {
-        // (one auxiliary stream per device: views whose prefixes run side by side on several
-        // prefix streams scan inline instead of coupling their streams through it)
-        int rc = use_aux ? aux_fork(s, &aux) : GSR_OK;
-        if (rc) return rc;
-    }
-    // every exit after the fork joins the auxiliary stream back first (the caller's stream stays
-    // ordered after the scan queued there, which writes into the caller's geometry buffer)
-    hipError_t e = launch_inclusive_scan(a.tiles_touched, nullptr, at<uint32_t>(gb, g.off[GEOM_EMIT_START]), P,
-                                         a.scan_status + scan_status_words(P), nullptr, aux, true);
-    if (e == hipSuccess && a.tile_diff) {  // the rects' difference array, beside the depth sort as well
-        ProfScope ps_(PK_RANGES, aux);
-        const TileHistJob hj = {a.rect4, P, a.tile_diff};
-        e = launch_tile_hist_batch(&hj, 1, a.grid_x, a.grid_y, aux);
-    }
-    if (e == hipSuccess && a.tile_diff) {  // ... and from it the tile ranges and the forward's tile order
-        ProfScope ps_(PK_TILE_ORDER, aux);
-        const OrderJob oj = diff_order_job(ib, width, height);
-        e = launch_tile_order_batch(&oj, 1, (int)(a.grid_x * a.grid_y), aux);
-    }
-
-    // 2. stable depth sort of the Gaussians
-    if (e == hipSuccess) {
-        ProfScope ps_(PK_DEPTH_SORT, s);
-        *dsort_out = depth_sort_job(gb, a, h_dev);
-        e = radix_sort_batch(dsort_out, 1, DEPTH_BITS, s);
-    }
-    if (debug && e == hipSuccess) e = hipStreamSynchronize(s);
-
-    // 3. instance offsets in depth order (cub::DeviceScan::InclusiveSum, rasterizer_impl.cu:280)
-    uint32_t* offsets = at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]);
-    *off_out = {offsets, offsets, P, a.scan_status, h_dev + 2};
-    if (e == hipSuccess) {
-        ProfScope ps_(PK_SCAN, s);
-        e = launch_inclusive_scan(offsets, nullptr, offsets, P, a.scan_status, h_dev + 2, s);
-    }
-    {
-        const int rc = aux_join(s, aux);
-        if (e != hipSuccess) return fail_hip(e, __LINE__);
-        if (rc) return rc;
-    }
-    DEBUG_SYNC(s);
-    return GSR_OK;
-}
-
-// Forward, first half: preprocess, depth sort and the tile-count scan are enqueued; *h_out is the
-// pinned word block the scan publishes num_rendered into (forward_geometry_wait reads it).
-static int forward_geometry_launch(char* geometry_buffer, char* image_buffer, int P, int D, int M, int width,
-                                   int height, const float* means3D, const float* dc, const float* shs,
-                                   const float* colors_precomp, const float* opacities, const float* scales,
-                                   float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                                   const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                                   float tan_fovx, float tan_fovy, bool prefiltered, bool antialiasing, int* radii,
-                                   bool debug, gsr_stream_t stream, uint32_t** h_out, SortJob* dsort_out,
-                                   ScanJob* off_out, int slot = 0, bool use_aux = true)
-{
-    hipStream_t s = (hipStream_t)stream;
-    PreprocessArgs a;
-    uint32_t* h_dev = nullptr;
-    int rc = forward_geometry_args(geometry_buffer, image_buffer, P, D, M, width, height, means3D, dc, shs,
-                                   colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                                   viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, antialiasing,
-                                   radii, slot, &a, h_out, &h_dev);
-    if (rc) return rc;
-    // 1. preprocess (forward.cu:154-272)
-    {
-        ProfScope ps_(PK_PREPROCESS, s);
-        HIP_TRY(launch_preprocess(a, s));
-    }
-    DEBUG_SYNC(s);
-    return forward_geometry_sort(a, geometry_buffer, image_buffer, width, height, P, h_dev, s, debug, use_aux,
-                                 dsort_out, off_out);
 }
 
 static int forward_geometry_wait(uint32_t* h, gsr_stream_t stream, int* num_rendered)
@@ -592,64 +482,19 @@ static int depth_sort_rerun_wide(SortJob* dsort, const ScanJob* off, uint32_t* c
     return GSR_OK;
 }
 
-// The single view's hand-off: waits for L; after a depth range too wide for three passes, this call's
-// depth sort runs again in four, `recount` (if any) enqueues again what the caller had put behind the
-// scan, and L is awaited once more.
-static int forward_geometry_wait_rerun(uint32_t* h, SortJob* dsort, const ScanJob* off, hipStream_t ps, int* L,
-                                       const std::function<int()>& recount)
-{
-    int rc = forward_geometry_wait(h, ps, L);
-    t_last_depth_passes[0] = depth_force_wide() ? 4 : 3;
-    if (rc == GSR_RERUN_WIDE) {
-        rc = depth_sort_rerun_wide(dsort, off, &h, 1, ps);
-        if (!rc && recount) rc = recount();
-        if (!rc) rc = forward_geometry_wait(h, ps, L);
-        t_last_depth_passes[0] = 4;
-    }
-    return rc;
-}
-
 int gsr_debug_last_depth_passes(int view) { return view >= 0 && view < MAX_VIEWS ? t_last_depth_passes[view] : 0; }
 
 int gsr_debug_grad_record_floats(void) { return GRAD_REC; }
-
-int gsr_forward_geometry_dc(char* geometry_buffer, char* image_buffer, int P, int D, int M, int width, int height,
-                         const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                         const float* opacities, const float* scales, float scale_modifier,
-                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                         const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
-                         bool prefiltered, bool antialiasing, int* radii, bool debug, gsr_stream_t stream,
-                         int* num_rendered)
-{
-    *num_rendered = 0;
-    if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
-    uint32_t* h = nullptr;
-    hipStream_t ps = nullptr;
-    int rc = prefix_begin((hipStream_t)stream, &ps);
-    if (rc) return rc;
-    SortJob dsort;
-    ScanJob off;
-    rc = forward_geometry_launch(geometry_buffer, image_buffer, P, D, M, width, height, means3D, dc, shs,
-                                 colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, antialiasing,
-                                 radii, debug, ps, &h, &dsort, &off);
-    if (rc) return rc;
-    rc = forward_geometry_wait_rerun(h, &dsort, &off, ps, num_rendered, nullptr);
-    const int rj = prefix_end((hipStream_t)stream, ps);
-    return rc ? rc : rj;
-}
-
-static int forward_render_impl(char* geometry_buffer, char* binning_buffer, char* image_buffer, int P,
-                               int num_rendered, const float* background, int width, int height, float* out_color,
-                               float* depth, bool debug, gsr_stream_t stream, hipStream_t prefix,
-                               bool counted = false);
 
 // The tile sort of one view (L > 0 instances) with the instance emission fused into its first
 // pass: the instances are generated from the depth-ordered rects; the sort's ping-pong buffers live
 // in the (not yet used) gradient-record region of the binning buffer, the first pass's count
 // matrix in the depth sort's ping-pong buffer (free by then).
-static TileSortJob fused_tile_sort_job(char* gb, char* bb, char* ib, int P, int L, int width, int height)
+// count_only: the job of the histogram phase (FUSED_COUNT), which needs neither L nor the binning buffer
+static TileSortJob fused_tile_sort_job(const Scene& sc, const ViewState& vs, int L, bool count_only)
 {
+    const int P = sc.P, width = sc.width, height = sc.height;
+    char *gb = vs.geometry, *ib = vs.image, *bb = vs.binning;
     const GeomLayout g = geom_layout(P);
     const ImageLayout im = image_layout(width, height);
     const BinLayout b = bin_layout(L);
@@ -666,7 +511,7 @@ static TileSortJob fused_tile_sort_job(char* gb, char* bb, char* ib, int P, int 
     // with the difference array the tile order writes every range and nothing reads the sorted
     // tile ids: no clearing of the ranges, no tile id written per instance
     j.ranges = diff ? nullptr : at<uint2>(ib, im.off[IMG_RANGES]);
-    if (!bb) return j;  // the histogram phase only (FUSED_COUNT): no binning buffer yet
+    if (count_only) return j;
     char* w = bb + b.off[BIN_GRAD_INST];
     j.k0 = reinterpret_cast<uint32_t*>(w + 2 * q);
     j.k1 = reinterpret_cast<uint32_t*>(w + 3 * q);
@@ -681,24 +526,12 @@ static TileSortJob fused_tile_sort_job(char* gb, char* bb, char* ib, int P, int 
     return j;
 }
 
-int gsr_forward_render(char* geometry_buffer, char* binning_buffer, char* image_buffer, int P, int num_rendered,
-                       const float* background, int width, int height, const float* colors_precomp,
-                       float* out_color, float* depth, int* radii, bool debug, gsr_stream_t stream)
-{
-    (void)radii;
-    (void)colors_precomp;
-    hipStream_t ps = nullptr;
-    const int rc = prefix_begin((hipStream_t)stream, &ps);
-    if (rc) return rc;
-    return forward_render_impl(geometry_buffer, binning_buffer, image_buffer, P, num_rendered, background, width,
-                               height, out_color, depth, debug, stream, ps);
-}
-
 // render_fwd's arguments for a view whose binning is complete
-static RenderFwdArgs render_fwd_args(char* gb, char* bb, char* ib, int P, int L, const float* background, int width,
-                                     int height, float* out_color, float* depth)
+static RenderFwdArgs render_fwd_args(const Scene& sc, const ViewState& vs, int L, const float* background)
 {
-    const GeomLayout g = geom_layout(P);
+    const int width = sc.width, height = sc.height;
+    char *gb = vs.geometry, *ib = vs.image, *bb = vs.binning;
+    const GeomLayout g = geom_layout(sc.P);
     const ImageLayout im = image_layout(width, height);
     const BinLayout b = bin_layout(L);
     RenderFwdArgs r;
@@ -712,65 +545,267 @@ static RenderFwdArgs render_fwd_args(char* gb, char* bb, char* ib, int P, int L,
     r.bg = background;
     r.final_T = at<float>(ib, im.off[IMG_FINAL_T]);
     r.n_contrib = at<uint32_t>(ib, im.off[IMG_N_CONTRIB]);
-    r.out_color = out_color;
-    r.invdepth = depth;
+    r.out_color = vs.out_color;
+    r.invdepth = vs.invdepth;
     r.hit = L > 0 ? at<uint8_t>(bb, b.off[BIN_HIT]) : nullptr;
     return r;
 }
 
-// Forward, second half: the tile sort (emission fused in), tile ranges and tile order on the
-// prefix stream, render_fwd on the caller's.
-// counted: the tile sort's first-pass histograms already ran (enqueued before the L read-back)
-static int forward_render_impl(char* geometry_buffer, char* binning_buffer, char* image_buffer, int P,
-                               int num_rendered, const float* background, int width, int height, float* out_color,
-                               float* depth, bool debug, gsr_stream_t stream, hipStream_t prefix, bool counted)
+// ---------------------------------------------------------------------------
+// The forward of V >= 1 views of the same Gaussians, in two stages split at the num_rendered
+// read-back.  Every stage is one launch over all views (grid.y = view).  What the entry points
+// differ in they decide themselves and pass in: the stream of the binning prefix (`ps`: the forked
+// prefix stream, or the caller's own) and the ForwardOptions.
+// ---------------------------------------------------------------------------
+enum PreprocessLauncher {
+    PREPROCESS_SINGLE,  // launch_preprocess: the one-view kernel instantiation (V == 1 only)
+    PREPROCESS_VIEWS    // launch_preprocess_views: the parameters and SH rows read once per 8 views
+};
+struct ForwardOptions {
+    PreprocessLauncher preprocess;
+    bool geometry_outputs;  // preprocess writes GeometryState's means2D, depths, rgb and conic_opacity
+    // the tile sort's first-pass histograms (FUSED_COUNT) need only the depth-ordered rects and offsets
+    // (not L or the binning buffer): enqueued before the read-back, they run while the host waits
+    bool early_count;
+};
+
+static int tile_sort_count_pass(const Scene& sc, const ViewState* vs, const int* which, int n, hipStream_t ps)
 {
-    // (colors_precomp was folded into the render record by preprocess)
-    hipStream_t s = prefix;
-    hipStream_t caller = (hipStream_t)stream;
-    if (P <= 0) return prefix_end(caller, prefix);
-    const int L = num_rendered;
-    const ImageLayout im = image_layout(width, height);
-    const BinLayout b = bin_layout(L);
-    char* gb = geometry_buffer;
-    char* ib = image_buffer;
-    char* bb = binning_buffer;
-    if (L > 0 && !bb) return fail(GSR_ERR_ALLOC, "null binning buffer");
-    const TileGrid tg(width, height);
-    uint32_t* sorted_tiles = L > 0 ? at<uint32_t>(bb, b.off[BIN_SORTED_TILES]) : nullptr;
-    if (L > 0) {
-        // stable sort by tile id over bits [0, msb(T)) of the depth-ordered instances
-        // (rasterizer_impl.cu:303-311 sorts [0, 32 + msb(T)) of the tile|depth keys)
-        const TileSortJob j = fused_tile_sort_job(gb, bb, ib, P, L, width, height);
-        ProfScope ps_(PK_TILE_SORT, s, counted);
-        HIP_TRY(tile_sort_fused_batch(&j, 1, tg.gx, tg.T, s, counted ? FUSED_SCATTER : FUSED_ALL));
-    }
-    DEBUG_SYNC(s);
-    uint2* ranges = at<uint2>(ib, im.off[IMG_RANGES]);
-    uint32_t* tile_order = at<uint32_t>(ib, im.off[IMG_TILE_ORDER]);
-    if (use_tile_diff(tg.gx, tg.gy)) {
-        // ranges and order: written from the rects' difference array by the geometry half (the
-        // auxiliary stream, joined before the tile-count scan)
-    } else {
-        {
-            ProfScope ps_(PK_RANGES, s);
-            HIP_TRY(launch_tile_ranges(L, sorted_tiles, ranges, tg.T, s));
-        }
-        DEBUG_SYNC(s);
-        ProfScope ps_(PK_TILE_ORDER, s);
-        HIP_TRY(launch_tile_order(ranges, nullptr, tg.T, tile_order, s));
-    }
-    {
-        const int rc = prefix_end(caller, prefix);
+    const TileGrid tg(sc.width, sc.height);
+    TileSortJob cj[MAX_VIEWS];
+    for (int i = 0; i < n; i++) cj[i] = fused_tile_sort_job(sc, vs[which[i]], 0, /*count_only=*/true);
+    ProfScope ps_(PK_TILE_SORT, ps);
+    HIP_TRY(tile_sort_fused_batch(cj, n, tg.gx, tg.T, ps, FUSED_COUNT));
+    return GSR_OK;
+}
+
+// Stage one (arguments checked, P > 0): preprocess, depth sort and the tile-count scan, then the one
+// host hand-off: L[v] = view v's num_rendered (all zero on failure).  View v uses pinned slot v.
+static int forward_geometry(const Scene& sc, int V, const Camera* cam, const ViewState* vs, const ForwardOptions& opt,
+                            hipStream_t ps, bool debug, int* L)
+{
+    const int P = sc.P;
+    const TileGrid tg(sc.width, sc.height);
+    const GeomLayout g = geom_layout(P);
+    for (int v = 0; v < V; v++) L[v] = 0;
+    uint32_t *h[MAX_VIEWS], *hdev[MAX_VIEWS];
+    PreprocessArgs pa[MAX_VIEWS];
+    for (int v = 0; v < V; v++) {
+        const int rc = preprocess_args(sc, cam[v], vs[v], v, opt.geometry_outputs, &pa[v], &h[v], &hdev[v]);
         if (rc) return rc;
     }
-    s = caller;
-    const RenderFwdArgs r = render_fwd_args(gb, bb, ib, P, L, background, width, height, out_color, depth);
+    // 1. preprocess (forward.cu:154-272)
     {
-        ProfScope ps_(PK_RENDER_FWD, s);
-        HIP_TRY(launch_render_fwd(r, tg.T, s));
+        ProfScope ps_(PK_PREPROCESS, ps);
+        HIP_TRY(opt.preprocess == PREPROCESS_SINGLE ? launch_preprocess(pa[0], ps) : launch_preprocess_views(pa, V, ps));
     }
-    DEBUG_SYNC(s);
+    DEBUG_SYNC(ps);
+    ScanJob rec[MAX_VIEWS], off[MAX_VIEWS];
+    SortJob dsort[MAX_VIEWS];
+    TileHistJob hj[MAX_VIEWS];
+    OrderJob dj[MAX_VIEWS];
+    for (int v = 0; v < V; v++) {
+        char* gb = vs[v].geometry;
+        const PreprocessArgs& a = pa[v];
+        rec[v] = {a.tiles_touched, at<uint32_t>(gb, g.off[GEOM_EMIT_START]), P, a.scan_status + scan_status_words(P),
+                  nullptr};
+        dsort[v] = depth_sort_job(gb, a, hdev[v]);
+        uint32_t* offsets = at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]);
+        off[v] = {offsets, offsets, P, a.scan_status, hdev[v] + 2};  // L -> the view's pinned word
+        hj[v] = {a.rect4, P, a.tile_diff};
+        dj[v] = diff_order_job(vs[v].image, sc.width, sc.height);
+    }
+    // 1b. each Gaussian's first gradient-record slot: index-order exclusive scan of the tile counts
+    //     (records in Gaussian order: preprocess_bwd's per-Gaussian gathers are contiguous), on the
+    //     auxiliary stream beside the depth sort; the tile sort's first pass (which reads it) waits for it
+    hipStream_t aux = ps;
+    int rc = stream_fork(g_aux, g_prefix_mode != 0, ps, &aux);
+    if (rc) return rc;
+    // every exit after the fork joins the auxiliary stream back first (the caller's stream stays
+    // ordered after the scans queued there, which write into the caller's geometry buffers)
+    hipError_t e = launch_scan_batch(rec, V, true, aux);
+    if (e == hipSuccess && use_tile_diff(tg.gx, tg.gy)) {  // the rects' difference arrays, beside the depth sorts as well
+        ProfScope ps_(PK_RANGES, aux);
+        e = launch_tile_hist_batch(hj, V, tg.gx, tg.gy, aux);
+    }
+    if (e == hipSuccess && use_tile_diff(tg.gx, tg.gy)) {  // ... and from them the tile ranges and the forward's tile orders
+        ProfScope ps_(PK_TILE_ORDER, aux);
+        e = launch_tile_order_batch(dj, V, tg.T, aux);
+    }
+    // 2. stable depth sort of the Gaussians
+    if (e == hipSuccess) {
+        ProfScope ps_(PK_DEPTH_SORT, ps);
+        e = radix_sort_batch(dsort, V, DEPTH_BITS, ps);
+    }
+    // 3. instance offsets in depth order (cub::DeviceScan::InclusiveSum, rasterizer_impl.cu:280); it
+    //    reads nothing the auxiliary stream writes, so it goes ahead of the join
+    if (e == hipSuccess) {
+        ProfScope ps_(PK_SCAN, ps);
+        e = launch_scan_batch(off, V, false, ps);
+    }
+    rc = stream_join(g_aux, ps, aux);
+    if (e != hipSuccess) return fail_hip(e, __LINE__);
+    if (rc) return rc;
+    if (opt.early_count) {
+        int all[MAX_VIEWS];
+        for (int v = 0; v < V; v++) all[v] = v;
+        rc = tile_sort_count_pass(sc, vs, all, V, ps);
+        if (rc) return rc;
+    }
+    DEBUG_SYNC(ps);
+    // 4. the one host hand-off: every view's num_rendered (rasterizer_impl.cu:283-284); a view whose depth
+    //    range was too wide for three passes re-runs its depth sort in four (this call only), and what
+    //    had been enqueued behind its scan -- the histograms -- runs again
+    int wide[MAX_VIEWS], nw = 0;
+    for (int v = 0; v < V && !rc; v++) {
+        rc = forward_geometry_wait(h[v], ps, &L[v]);
+        t_last_depth_passes[v] = depth_force_wide() ? 4 : 3;
+        if (rc == GSR_RERUN_WIDE) {
+            wide[nw++] = v;
+            rc = GSR_OK;
+        }
+    }
+    if (!rc && nw) {
+        SortJob wj[MAX_VIEWS];
+        ScanJob wo[MAX_VIEWS];
+        uint32_t* wh[MAX_VIEWS];
+        for (int i = 0; i < nw; i++) {
+            wj[i] = dsort[wide[i]];
+            wo[i] = off[wide[i]];
+            wh[i] = h[wide[i]];
+            t_last_depth_passes[wide[i]] = 4;
+        }
+        rc = depth_sort_rerun_wide(wj, wo, wh, nw, ps);
+        if (!rc && opt.early_count) rc = tile_sort_count_pass(sc, vs, wide, nw, ps);
+        for (int i = 0; i < nw && !rc; i++) rc = forward_geometry_wait(h[wide[i]], ps, &L[wide[i]]);
+    }
+    if (rc)
+        for (int v = 0; v < V; v++) L[v] = 0;
+    return rc;
+}
+
+// Stage two, for the n views which[0..n) whose binning buffers hold their L[v] instances: the tile
+// sort (emission fused in), tile ranges and tile order on the prefix stream `ps`, which is joined
+// back into the caller's; then every view's render_fwd in one launch on the caller's.
+// counted: the tile sort's first-pass histograms already ran (ForwardOptions::early_count)
+static int forward_render(const Scene& sc, const ViewState* vs, const int* L, const int* which, int n,
+                          const float* background, bool counted, hipStream_t caller, hipStream_t ps, bool debug)
+{
+    // (colors_precomp was folded into the render record by preprocess)
+    const TileGrid tg(sc.width, sc.height);
+    const ImageLayout im = image_layout(sc.width, sc.height);
+    TileSortJob tsort[MAX_VIEWS];
+    RangesJob rj[MAX_VIEWS];
+    OrderJob oj[MAX_VIEWS];
+    RenderFwdArgs ra[MAX_VIEWS];
+    int ns = 0;
+    for (int k = 0; k < n; k++) {
+        const ViewState& s = vs[which[k]];
+        const int Lv = L[which[k]];
+        if (Lv > 0) tsort[ns++] = fused_tile_sort_job(sc, s, Lv, /*count_only=*/false);
+        uint2* ranges = at<uint2>(s.image, im.off[IMG_RANGES]);
+        rj[k] = {Lv, Lv > 0 ? at<uint32_t>(s.binning, bin_layout(Lv).off[BIN_SORTED_TILES]) : nullptr, ranges};
+        oj[k] = {ranges, nullptr, at<uint32_t>(s.image, im.off[IMG_TILE_ORDER])};
+        ra[k] = render_fwd_args(sc, s, Lv, background);
+    }
+    if (ns) {
+        // stable sort by tile id over bits [0, msb(T)) of the depth-ordered instances
+        // (rasterizer_impl.cu:303-311 sorts [0, 32 + msb(T)) of the tile|depth keys)
+        ProfScope ps_(PK_TILE_SORT, ps, counted);
+        HIP_TRY(tile_sort_fused_batch(tsort, ns, tg.gx, tg.T, ps, counted ? FUSED_SCATTER : FUSED_ALL));
+    }
+    DEBUG_SYNC(ps);
+    // (with the difference array: ranges and orders were written by stage one, on the auxiliary
+    // stream, joined before the tile sort's first pass)
+    if (n && !use_tile_diff(tg.gx, tg.gy)) {
+        {
+            ProfScope ps_(PK_RANGES, ps);
+            HIP_TRY(launch_tile_ranges_batch(rj, n, tg.T, ps));
+        }
+        DEBUG_SYNC(ps);
+        ProfScope ps_(PK_TILE_ORDER, ps);
+        HIP_TRY(launch_tile_order_batch(oj, n, tg.T, ps));
+    }
+    DEBUG_SYNC(ps);
+    const int rc = stream_join(g_prefix, caller, ps);
+    if (rc) return rc;
+    if (n) {  // every view's render in one launch (one launch tail per batch)
+        ProfScope ps_(PK_RENDER_FWD, caller);
+        HIP_TRY(launch_render_fwd_batch(ra, n, tg.T, caller));
+    }
+    DEBUG_SYNC(caller);
+    return GSR_OK;
+}
+
+// a view's binning buffer holds L instances (else the view is left to the caller: allocate
+// gsr_binning_buffer_size(L), then gsr_forward_render)
+static bool binning_fits(const ViewState& vs, int L)
+{
+    return vs.binning && gsr_binning_buffer_size(L) <= vs.binning_capacity;
+}
+
+int gsr_forward_geometry_dc(char* geometry_buffer, char* image_buffer, int P, int D, int M, int width, int height,
+                         const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                         const float* opacities, const float* scales, float scale_modifier,
+                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                         const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                         bool prefiltered, bool antialiasing, int* radii, bool debug, gsr_stream_t stream,
+                         int* num_rendered)
+{
+    *num_rendered = 0;
+    if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, prefiltered, antialiasing, width, height};
+    const Camera cam = {viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy};
+    const ViewState vs = {geometry_buffer, image_buffer, nullptr, 0, nullptr, nullptr, radii};
+    int rc = forward_args_check(sc, vs);
+    if (rc) return rc;
+    hipStream_t caller = (hipStream_t)stream, ps = nullptr;
+    rc = stream_fork(g_prefix, g_prefix_mode == 1, caller, &ps);
+    if (rc) return rc;
+    // (no binning buffer yet, and the caller allocates it before gsr_forward_render: no early count pass)
+    const ForwardOptions opt = {PREPROCESS_SINGLE, /*geometry_outputs=*/true, /*early_count=*/false};
+    rc = forward_geometry(sc, 1, &cam, &vs, opt, ps, debug, num_rendered);
+    const int rj = stream_join(g_prefix, caller, ps);
+    return rc ? rc : rj;
+}
+
+int gsr_forward_render(char* geometry_buffer, char* binning_buffer, char* image_buffer, int P, int num_rendered,
+                       const float* background, int width, int height, const float* colors_precomp,
+                       float* out_color, float* depth, int* radii, bool debug, gsr_stream_t stream)
+{
+    (void)radii;
+    (void)colors_precomp;
+    if (P <= 0) return GSR_OK;
+    if (num_rendered > 0 && !binning_buffer) return fail(GSR_ERR_ALLOC, "null binning buffer");
+    Scene sc = {};
+    sc.P = P; sc.width = width; sc.height = height;  // (all that stage two reads)
+    const ViewState vs = {geometry_buffer, image_buffer, binning_buffer, 0, out_color, depth, nullptr};
+    hipStream_t caller = (hipStream_t)stream, ps = nullptr;
+    int rc = stream_fork(g_prefix, g_prefix_mode == 1, caller, &ps);
+    if (rc) return rc;
+    const int view = 0;
+    rc = forward_render(sc, &vs, &num_rendered, &view, 1, background, /*counted=*/false, caller, ps, debug);
+    if (rc) stream_join(g_prefix, caller, ps);
+    return rc;
+}
+
+// Both stages of a forward whose binning buffers the caller sized in advance (gsr_forward_prealloc_dc,
+// gsr_forward_views; arguments checked, P > 0).  A view whose buffer is too small is left unrendered.
+static int forward_prealloc(const Scene& sc, int V, const Camera* cam, const ViewState* vs, const float* background,
+                            const ForwardOptions& opt, hipStream_t caller, hipStream_t ps, bool debug,
+                            int* num_rendered, int* rendered)
+{
+    int rc = forward_geometry(sc, V, cam, vs, opt, ps, debug, num_rendered);
+    int fit[MAX_VIEWS], nf = 0;
+    for (int v = 0; v < V && !rc; v++)
+        if (binning_fits(vs[v], num_rendered[v])) fit[nf++] = v;
+    if (!rc) rc = forward_render(sc, vs, num_rendered, fit, nf, background, opt.early_count, caller, ps, debug);
+    if (rc) {
+        stream_join(g_prefix, caller, ps);
+        return rc;
+    }
+    for (int k = 0; k < nf; k++) rendered[fit[k]] = 1;
     return GSR_OK;
 }
 
@@ -810,49 +845,20 @@ int gsr_forward_prealloc_dc(char* geometry_buffer, char* image_buffer, char* bin
                          float* out_color, float* depth, int* radii, bool debug, gsr_stream_t stream,
                          int* num_rendered, int* rendered)
 {
-    (void)colors_precomp;
     *rendered = 0;
     *num_rendered = 0;
     if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
-    uint32_t* h = nullptr;
-    hipStream_t ps = nullptr;
-    int rc = prefix_begin((hipStream_t)stream, &ps);
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, prefiltered, antialiasing, width, height};
+    const Camera cam = {viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy};
+    const ViewState vs = {geometry_buffer, image_buffer, binning_buffer, binning_capacity, out_color, depth, radii};
+    int rc = forward_args_check(sc, vs);
     if (rc) return rc;
-    SortJob dsort;
-    ScanJob off;
-    rc = forward_geometry_launch(geometry_buffer, image_buffer, P, D, M, width, height, means3D, dc, shs,
-                                 colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, antialiasing,
-                                 radii, debug, ps, &h, &dsort, &off);
+    hipStream_t caller = (hipStream_t)stream, ps = nullptr;
+    rc = stream_fork(g_prefix, g_prefix_mode == 1, caller, &ps);
     if (rc) return rc;
-    // the tile sort's first-pass histograms need only the depth-ordered rects and offsets (not L or
-    // the binning buffer): enqueued before the read-back, they run while the host waits
-    auto count_pass = [&]() -> int {
-        const TileGrid tg(width, height);
-        const TileSortJob cj = fused_tile_sort_job(geometry_buffer, nullptr, image_buffer, P, 0, width, height);
-        ProfScope ps_(PK_TILE_SORT, ps);
-        const hipError_t e = tile_sort_fused_batch(&cj, 1, tg.gx, tg.T, ps, FUSED_COUNT);
-        return e == hipSuccess ? GSR_OK : fail_hip(e, __LINE__);
-    };
-    rc = count_pass();
-    if (rc) {
-        prefix_end((hipStream_t)stream, ps);
-        return rc;
-    }
-    int L = 0;
-    rc = forward_geometry_wait_rerun(h, &dsort, &off, ps, &L, count_pass);  // (a re-run: the histograms again)
-    *num_rendered = L;
-    if (rc) {
-        prefix_end((hipStream_t)stream, ps);
-        return rc;
-    }
-    if (!binning_buffer || gsr_binning_buffer_size(L) > binning_capacity)  // caller allocates
-        return prefix_end((hipStream_t)stream, ps);
-    rc = forward_render_impl(geometry_buffer, binning_buffer, image_buffer, P, L, background, width, height,
-                             out_color, depth, debug, stream, ps, true);
-    if (rc) return rc;
-    *rendered = 1;
-    return GSR_OK;
+    const ForwardOptions opt = {PREPROCESS_SINGLE, /*geometry_outputs=*/true, /*early_count=*/true};
+    return forward_prealloc(sc, 1, &cam, &vs, background, opt, caller, ps, debug, num_rendered, rendered);
 }
 
 int gsr_forward_views(int V, int P, int D, int M, const float* background, int width, int height,
@@ -874,192 +880,36 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
         rendered[v] = 0;
     }
     if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
-    hipStream_t caller = (hipStream_t)stream;
-    const TileGrid tg(width, height);
-    const GeomLayout g = geom_layout(P);
-    const ImageLayout im = image_layout(width, height);
-
-    uint32_t* h[MAX_VIEWS];
-    PreprocessArgs pa[MAX_VIEWS];
-    uint32_t* hdev[MAX_VIEWS];
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, prefiltered, antialiasing, width, height};
+    Camera cam[MAX_VIEWS];
+    ViewState vs[MAX_VIEWS];
     for (int v = 0; v < V; v++) {
-        if (!geometry_buffers[v] || !image_buffers[v]) return fail(GSR_ERR_ALLOC, "null state buffer");
-        if (!out_colors[v] || !out_invdepths[v]) return fail(GSR_ERR_INVALID, "null per-view output");
-        const int rc = forward_geometry_args(geometry_buffers[v], image_buffers[v], P, D, M, width, height, means3D, dc,
-                                             shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                                             cov3D_precomp, viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v],
-                                             tan_fovy[v], prefiltered, antialiasing, radii ? radii[v] : nullptr, v,
-                                             &pa[v], &h[v], &hdev[v]);
+        cam[v] = {viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v], tan_fovy[v]};
+        vs[v] = {geometry_buffers[v], image_buffers[v], binning_buffers[v], binning_capacity[v], out_colors[v],
+                 out_invdepths[v], radii ? radii[v] : nullptr};
+        if (!vs[v].geometry || !vs[v].image) return fail(GSR_ERR_ALLOC, "null state buffer");
+        if (!vs[v].out_color || !vs[v].invdepth) return fail(GSR_ERR_INVALID, "null per-view output");
+        const int rc = forward_args_check(sc, vs[v]);
         if (rc) return rc;
-        // GeometryState's means2D, depths, rgb and conic_opacity are read by nothing after the forward: the
-        // batched forward does not write them (40 B per visible Gaussian and view)
-        pa[v].means2D = nullptr;
-        pa[v].depths = nullptr;
-        pa[v].rgb = nullptr;
-        pa[v].conic_opacity = nullptr;  // (preprocess_bwd recomputes it: 16 B per visible Gaussian and view)
     }
-    // The binning prefix of all V views, batched: every stage is one launch over all views
-    // (grid.y = view), on the caller's stream like the renders that follow (a separate prefix
-    // stream would overlap nothing here -- it would fork from the caller's previous work and the
-    // render would join it -- and each hop between the queues costs ~10 us of idle GPU).
-    hipStream_t ps = caller;
-    int rc = GSR_OK;
-    {
-        ProfScope ps_(PK_PREPROCESS, ps);
-        HIP_TRY(launch_preprocess_views(pa, V, ps));  // the parameters and SH rows read once per 8 views
-    }
-    DEBUG_SYNC(ps);
-    ScanJob rec[MAX_VIEWS], off[MAX_VIEWS];
-    SortJob dsort[MAX_VIEWS];
-    for (int v = 0; v < V; v++) {
-        char* gb = geometry_buffers[v];
-        const PreprocessArgs& a = pa[v];
-        // each Gaussian's first gradient-record slot (index-order exclusive scan of the tile counts)
-        rec[v] = {a.tiles_touched, at<uint32_t>(gb, g.off[GEOM_EMIT_START]), P, a.scan_status + scan_status_words(P),
-                  nullptr};
-        dsort[v] = depth_sort_job(gb, a, hdev[v]);
-        uint32_t* offsets = at<uint32_t>(gb, g.off[GEOM_POINT_OFFSETS]);
-        off[v] = {offsets, offsets, P, a.scan_status, hdev[v] + 2};  // L -> the view's pinned word
-    }
-    // the record-slot scans (read only by the fused tile sort) on the auxiliary stream, beside the
-    // depth sorts
-    hipStream_t aux = ps;
-    rc = aux_fork(ps, &aux);
-    if (rc) return rc;
-    {
-        // every exit after the fork joins the auxiliary stream back first: the caller's stream
-        // must stay ordered after what is already queued there (it writes the caller's buffers)
-        hipError_t e = launch_scan_batch(rec, V, true, aux);
-        if (e == hipSuccess && use_tile_diff(tg.gx, tg.gy)) {  // the rects' difference arrays, beside the depth sorts
-            TileHistJob hj[MAX_VIEWS];
-            for (int v = 0; v < V; v++) hj[v] = {pa[v].rect4, P, pa[v].tile_diff};
-            {
-                ProfScope ps_(PK_RANGES, aux);
-                e = launch_tile_hist_batch(hj, V, tg.gx, tg.gy, aux);
-            }
-            if (e == hipSuccess) {  // the views' tile ranges and forward tile orders, beside the sorts
-                OrderJob dj[MAX_VIEWS];
-                for (int v = 0; v < V; v++) dj[v] = diff_order_job(image_buffers[v], width, height);
-                ProfScope ps_(PK_TILE_ORDER, aux);
-                e = launch_tile_order_batch(dj, V, tg.T, aux);
-            }
-        }
-        if (e == hipSuccess) {
-            ProfScope ps_(PK_DEPTH_SORT, ps);
-            e = radix_sort_batch(dsort, V, DEPTH_BITS, ps);
-        }
-        rc = aux_join(ps, aux);
-        if (e != hipSuccess) return fail_hip(e, __LINE__);
-    }
-    if (rc) return rc;
-    {
-        ProfScope ps_(PK_SCAN, ps);
-        HIP_TRY(launch_scan_batch(off, V, false, ps));
-    }
-    // the first tile-sort pass's histograms need only the depth-ordered rects and offsets: the GPU
-    // computes them while the host waits for L below
-    auto count_pass = [&](const int* which, int n) -> hipError_t {
-        TileSortJob cj[MAX_VIEWS];
-        for (int i = 0; i < n; i++)
-            cj[i] = fused_tile_sort_job(geometry_buffers[which[i]], nullptr, image_buffers[which[i]], P, 0, width, height);
-        ProfScope ps_(PK_TILE_SORT, ps);
-        return tile_sort_fused_batch(cj, n, tg.gx, tg.T, ps, FUSED_COUNT);
-    };
-    {
-        int all[MAX_VIEWS];
-        for (int v = 0; v < V; v++) all[v] = v;
-        HIP_TRY(count_pass(all, V));
-    }
-    DEBUG_SYNC(ps);
-    // the one host hand-off: every view's num_rendered (rasterizer_impl.cu:283-284); a view whose depth
-    // range was too wide for three passes re-runs its depth sort in four (this call only)
-    int L[MAX_VIEWS];
-    int wide[MAX_VIEWS], nw = 0;
-    for (int v = 0; v < V && !rc; v++) {
-        rc = forward_geometry_wait(h[v], ps, &L[v]);
-        t_last_depth_passes[v] = depth_force_wide() ? 4 : 3;
-        if (rc == GSR_RERUN_WIDE) {
-            wide[nw++] = v;
-            rc = GSR_OK;
-        }
-    }
-    if (!rc && nw) {
-        SortJob wj[MAX_VIEWS];
-        ScanJob wo[MAX_VIEWS];
-        uint32_t* wh[MAX_VIEWS];
-        for (int i = 0; i < nw; i++) {
-            wj[i] = dsort[wide[i]];
-            wo[i] = off[wide[i]];
-            wh[i] = h[wide[i]];
-            t_last_depth_passes[wide[i]] = 4;
-        }
-        rc = depth_sort_rerun_wide(wj, wo, wh, nw, ps);
-        if (!rc) {
-            const hipError_t e = count_pass(wide, nw);
-            if (e != hipSuccess) rc = fail_hip(e, __LINE__);
-        }
-        for (int i = 0; i < nw && !rc; i++) rc = forward_geometry_wait(h[wide[i]], ps, &L[wide[i]]);
-    }
-    for (int v = 0; v < V; v++) num_rendered[v] = rc ? 0 : L[v];
-    if (rc) {
-        prefix_end(caller, ps);
-        return rc;
-    }
-    // views whose binning buffer holds them: emission fused into the tile sort, tile ranges and
-    // tile order, batched (the others are left to the caller: allocate
-    // gsr_binning_buffer_size(num_rendered[v]), then gsr_forward_render)
-    int fit[MAX_VIEWS], nf = 0;
-    TileSortJob tsort[MAX_VIEWS];
-    RangesJob rj[MAX_VIEWS];
-    OrderJob oj[MAX_VIEWS];
-    int ns = 0;
-    for (int v = 0; v < V; v++) {
-        if (!binning_buffers[v] || binning_capacity[v] == 0 || gsr_binning_buffer_size(L[v]) > binning_capacity[v])
-            continue;
-        char* bb = binning_buffers[v];
-        char* ib = image_buffers[v];
-        char* gb = geometry_buffers[v];
-        const BinLayout b = bin_layout(L[v]);
-        if (L[v] > 0) tsort[ns++] = fused_tile_sort_job(gb, bb, ib, P, L[v], width, height);
-        rj[nf] = {L[v], L[v] > 0 ? at<uint32_t>(bb, b.off[BIN_SORTED_TILES]) : nullptr, at<uint2>(ib, im.off[IMG_RANGES])};
-        oj[nf] = {at<uint2>(ib, im.off[IMG_RANGES]), nullptr, at<uint32_t>(ib, im.off[IMG_TILE_ORDER])};
-        fit[nf++] = v;
-    }
-    if (ns) {
-        ProfScope ps_(PK_TILE_SORT, ps, true);
-        HIP_TRY(tile_sort_fused_batch(tsort, ns, tg.gx, tg.T, ps, FUSED_SCATTER));
-    }
-    if (nf && !use_tile_diff(tg.gx, tg.gy)) {  // (with the difference array: ranges and orders are done)
-        {
-            ProfScope ps_(PK_RANGES, ps);
-            HIP_TRY(launch_tile_ranges_batch(rj, nf, tg.T, ps));
-        }
-        ProfScope ps_(PK_TILE_ORDER, ps);
-        HIP_TRY(launch_tile_order_batch(oj, nf, tg.T, ps));
-    }
-    DEBUG_SYNC(ps);
-    rc = prefix_end(caller, ps);
-    if (rc) return rc;
-    RenderFwdArgs ra[MAX_VIEWS];
-    for (int k = 0; k < nf; k++) {
-        const int v = fit[k];
-        ra[k] = render_fwd_args(geometry_buffers[v], binning_buffers[v], image_buffers[v], P, L[v], background, width,
-                                height, out_colors[v], out_invdepths[v]);
-        rendered[v] = 1;
-    }
-    if (nf) {  // every view's render in one launch (one launch tail per batch)
-        ProfScope ps_(PK_RENDER_FWD, caller);
-        HIP_TRY(launch_render_fwd_batch(ra, nf, tg.T, caller));
-    }
-    DEBUG_SYNC(caller);
-    return GSR_OK;
+    // The binning prefix of all V views on the caller's stream, like the renders that follow (a
+    // separate prefix stream would overlap nothing here -- it would fork from the caller's previous
+    // work and the render would join it -- and each hop between the queues costs ~10 us of idle GPU).
+    hipStream_t caller = (hipStream_t)stream;
+    // GeometryState's means2D, depths, rgb and conic_opacity are read by nothing after the forward:
+    // the batched forward does not write them
+    const ForwardOptions opt = {PREPROCESS_VIEWS, /*geometry_outputs=*/false, /*early_count=*/true};
+    return forward_prealloc(sc, V, cam, vs, background, opt, caller, caller, debug, num_rendered, rendered);
 }
 
 // render_bwd's arguments for one view (P, R > 0)
-static RenderBwdArgs render_bwd_args(int P, int R, const float* background, int width, int height, char* gb,
-                                     char* bb, char* ib, const float* dL_dpix, const float* dL_invdepths)
+static RenderBwdArgs render_bwd_args(const Scene& sc, const ViewState& vs, int R, const float* background,
+                                     const float* dL_dpix, const float* dL_invdepths)
 {
-    const GeomLayout g = geom_layout(P);
+    const int width = sc.width, height = sc.height;
+    char *gb = vs.geometry, *ib = vs.image, *bb = vs.binning;
+    const GeomLayout g = geom_layout(sc.P);
     const ImageLayout im = image_layout(width, height);
     const BinLayout b = bin_layout(R);
     const TileGrid tg(width, height);
@@ -1087,14 +937,14 @@ static RenderBwdArgs render_bwd_args(int P, int R, const float* background, int 
 
 // BACKWARD::render of one view (rasterizer_impl.cu:399-418; P, R > 0): the backward's tile order
 // (longest n_contrib first), then the per-(tile, Gaussian) gradient records
-static int backward_render_impl(int P, int R, const float* background, int width, int height, char* gb, char* bb,
-                                char* ib, const float* dL_dpix, const float* dL_invdepths, bool debug, hipStream_t s)
+static int backward_render_impl(const Scene& sc, const ViewState& vs, int R, const float* background,
+                                const float* dL_dpix, const float* dL_invdepths, bool debug, hipStream_t s)
 {
-    const ImageLayout im = image_layout(width, height);
-    const RenderBwdArgs r = render_bwd_args(P, R, background, width, height, gb, bb, ib, dL_dpix, dL_invdepths);
+    const ImageLayout im = image_layout(sc.width, sc.height);
+    const RenderBwdArgs r = render_bwd_args(sc, vs, R, background, dL_dpix, dL_invdepths);
     {
         ProfScope ps_(PK_TILE_ORDER, s);
-        HIP_TRY(launch_tile_order(nullptr, r.tile_work, r.T, at<uint32_t>(ib, im.off[IMG_TILE_ORDER]), s));
+        HIP_TRY(launch_tile_order(nullptr, r.tile_work, r.T, at<uint32_t>(vs.image, im.off[IMG_TILE_ORDER]), s));
     }
     {
         ProfScope ps_(PK_RENDER_BWD, s);  // valid[] was cleared by the forward's tile sort
@@ -1107,46 +957,45 @@ static int backward_render_impl(int P, int R, const float* background, int width
 // What the single-view and the batched preprocess_bwd share: the argument checks, the per-Gaussian
 // parameters and the gradient outputs (the single view's extras -- radii, dL_dconic, dL_dinvdepth --
 // stay null here).
-static int preprocess_bwd_shared(PreprocessBwdArgs& p, int P, int D, int M, int width, int height,
-                                 const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                                 const float* opacities, const float* scales, float scale_modifier,
-                                 const float* rotations, const float* cov3D_precomp, bool has_invdepth,
-                                 bool antialiasing, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D,
-                                 float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                 unsigned accumulate)
+static int preprocess_bwd_shared(PreprocessBwdArgs& p, const Scene& sc, bool has_invdepth, float* dL_dcolor,
+                                 float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
+                                 float* dL_dsh, float* dL_dscale, float* dL_drot, unsigned accumulate)
 {
     if (accumulate & ~(unsigned)GSR_ACC_ALL) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
-    if (dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
-    if (dc && colors_precomp)
+    if (sc.dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
+    if (sc.dc && sc.colors_precomp)
         return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M > 0 && (!shs || !dL_dsh)) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
-    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
-    p.means3D = means3D; p.radii = nullptr; p.shs = shs; p.dc = dc; p.dL_ddc = dc ? dL_ddc : nullptr;
-    p.opacities = opacities; p.scales = scales; p.rotations = rotations; p.scale_modifier = scale_modifier;
-    p.cov3D_precomp = cov3D_precomp;
-    p.antialiasing = antialiasing;
+    if (sc.dc && sc.M > 0 && (!sc.shs || !dL_dsh))
+        return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
+    p.P = sc.P; p.D = sc.D; p.M = sc.dc ? sc.M + 1 : sc.M;
+    p.means3D = sc.means3D; p.radii = nullptr; p.shs = sc.shs; p.dc = sc.dc; p.dL_ddc = sc.dc ? dL_ddc : nullptr;
+    p.opacities = sc.opacities; p.scales = sc.scales; p.rotations = sc.rotations;
+    p.scale_modifier = sc.scale_modifier;
+    p.cov3D_precomp = sc.cov3D_precomp;
+    p.antialiasing = sc.antialiasing;
     p.has_invdepth = has_invdepth;
-    p.W = width; p.H = height;
+    p.W = sc.width; p.H = sc.height;
     p.dL_dconic = nullptr; p.dL_dinvdepth = nullptr;
     p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (shs && M > 0) ? dL_dsh : nullptr;
+    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (sc.shs && sc.M > 0) ? dL_dsh : nullptr;
     p.dL_dscale = dL_dscale; p.dL_drot = dL_drot;
     p.acc = accumulate;
     return GSR_OK;
 }
 
-// One view's part of preprocess_bwd's arguments (L: its num_rendered; bb may be null when L == 0)
-static BwdView bwd_view(char* gb, char* bb, int P, int L, int width, int height, const float* viewmatrix,
-                        const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+// One view's part of preprocess_bwd's arguments (L: its num_rendered; vs.binning may be null when
+// L == 0; radii: what the forward wrote, null for the GeometryState's own)
+static BwdView bwd_view(const Scene& sc, const Camera& cam, const ViewState& vs, int L, const int* radii,
                         float* dL_dmean2D)
 {
-    const GeomLayout g = geom_layout(P);
+    char *gb = vs.geometry, *bb = vs.binning;
+    const GeomLayout g = geom_layout(sc.P);
     const BinLayout b = bin_layout(L);
     BwdView bv;
-    bv.view = viewmatrix; bv.proj = projmatrix; bv.campos = campos;
-    bv.focal_y = height / (2.0f * tan_fovy);
-    bv.focal_x = width / (2.0f * tan_fovx);
-    bv.tan_fovx = tan_fovx; bv.tan_fovy = tan_fovy;
+    bv.view = cam.view; bv.proj = cam.proj; bv.campos = cam.campos;
+    bv.focal_y = sc.height / (2.0f * cam.tan_fovy);
+    bv.focal_x = sc.width / (2.0f * cam.tan_fovx);
+    bv.tan_fovx = cam.tan_fovx; bv.tan_fovy = cam.tan_fovy;
     bv.radii = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
     bv.conic_opacity = at<float4>(gb, g.off[GEOM_CONIC_OPACITY]);
     bv.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
@@ -1170,11 +1019,13 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
                         float* dL_dscale, float* dL_drot, bool antialiasing, bool debug, unsigned accumulate,
                         gsr_stream_t stream)
 {
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
+    const Camera cam = {viewmatrix, projmatrix, campos, tan_fovx, tan_fovy};
+    const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, nullptr};
     PreprocessBwdViewsArgs A;
-    int rc = preprocess_bwd_shared(A.a, P, D, M, width, height, means3D, dc, shs, colors_precomp, opacities, scales,
-                                   scale_modifier, rotations, cov3D_precomp, dL_invdepths != nullptr, antialiasing,
-                                   dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
-                                   accumulate);
+    int rc = preprocess_bwd_shared(A.a, sc, dL_invdepths != nullptr, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D,
+                                   dL_ddc, dL_dsh, dL_dscale, dL_drot, accumulate);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (P <= 0) return GSR_OK;
@@ -1182,8 +1033,7 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
     if ((dL_invdepths == nullptr) != (dL_dinvdepth == nullptr) && dL_dinvdepth == nullptr)
         return fail(GSR_ERR_INVALID, "dL_dinvdepth must be given with dL_invdepths");
     if (R > 0) {  // (no instances: no records to write)
-        rc = backward_render_impl(P, R, background, width, height, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                  dL_invdepths, debug, s);
+        rc = backward_render_impl(sc, vs, R, background, dL_dpix, dL_invdepths, debug, s);
         if (rc) return rc;
     }
     // BACKWARD::preprocess (rasterizer_impl.cu:423-449), with the per-Gaussian gather of the records:
@@ -1192,8 +1042,7 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
     A.V = 1;
     A.g_begin = 0;
     A.g_end = P;
-    A.v[0] = bwd_view(geom_buffer, binning_buffer, P, R, width, height, viewmatrix, projmatrix, campos, tan_fovx,
-                      tan_fovy, radii, dL_dmean2D);
+    A.v[0] = bwd_view(sc, cam, vs, R, radii, dL_dmean2D);
     A.a.radii = A.v[0].radii;
     A.a.dL_dconic = dL_dconic;
     A.a.dL_dinvdepth = dL_dinvdepth;
@@ -1231,8 +1080,10 @@ int gsr_backward_render(int P, int R, const float* background, int width, int he
     if (P == 0 || R == 0) return GSR_OK;
     if (!geom_buffer || !image_buffer || !binning_buffer) return fail(GSR_ERR_ALLOC, "null state buffer");
     if (!dL_dpix) return fail(GSR_ERR_INVALID, "null dL_dpix");
-    return backward_render_impl(P, R, background, width, height, geom_buffer, binning_buffer, image_buffer, dL_dpix,
-                                dL_invdepths, debug, s);
+    Scene sc = {};
+    sc.P = P; sc.width = width; sc.height = height;  // (all that BACKWARD::render reads)
+    const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, nullptr};
+    return backward_render_impl(sc, vs, R, background, dL_dpix, dL_invdepths, debug, s);
 }
 
 int gsr_backward_preprocess_views(int V, int P, int D, int M, const int* R, int width, int height,
@@ -1270,13 +1121,13 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
 {
     if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
     if (g_begin < 0 || g_end > P || g_begin > g_end) return fail(GSR_ERR_INVALID, "range outside [0, P)");
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
     PreprocessBwdViewsArgs A;
     // a view rendered without an inverse-depth gradient has zero invdepth fields in its records:
     // subtracting their (zero) term leaves its gradients bit-identical
-    const int rc = preprocess_bwd_shared(A.a, P, D, M, width, height, means3D, dc, shs, colors_precomp, opacities,
-                                         scales, scale_modifier, rotations, cov3D_precomp, has_invdepth, antialiasing,
-                                         dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale,
-                                         dL_drot, accumulate);
+    const int rc = preprocess_bwd_shared(A.a, sc, has_invdepth, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc,
+                                         dL_dsh, dL_dscale, dL_drot, accumulate);
     if (rc) return rc;
     if (!R || !viewmatrices || !projmatrices || !campos || !tan_fovx || !tan_fovy || !geom_buffers ||
         !binning_buffers || !dL_dmean2D)
@@ -1289,8 +1140,9 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
     for (int v = 0; v < V; v++) {
         if (!geom_buffers[v] || (R[v] > 0 && !binning_buffers[v])) return fail(GSR_ERR_ALLOC, "null state buffer");
         if (!dL_dmean2D[v]) return fail(GSR_ERR_INVALID, "null per-view gradient");
-        A.v[v] = bwd_view(geom_buffers[v], binning_buffers[v], P, R[v], width, height, viewmatrices[v], projmatrices[v],
-                          campos[v], tan_fovx[v], tan_fovy[v], radii ? radii[v] : nullptr, dL_dmean2D[v]);
+        const Camera cam = {viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v], tan_fovy[v]};
+        const ViewState vs = {geom_buffers[v], nullptr, binning_buffers[v], 0, nullptr, nullptr, nullptr};
+        A.v[v] = bwd_view(sc, cam, vs, R[v], radii ? radii[v] : nullptr, dL_dmean2D[v]);
     }
     // BACKWARD::preprocess (rasterizer_impl.cu:423-449) of the whole batch: one pass over the Gaussians
     {
@@ -1323,6 +1175,8 @@ int gsr_backward_render_views(int V, int P, const int* R, const float* backgroun
                         at<uint32_t>(image_buffers[v], im.off[IMG_TILE_ORDER])};
     }
     // BACKWARD::render of every view (its per-(tile, Gaussian) records), one launch per batch
+    Scene sc = {};
+    sc.P = P; sc.width = width; sc.height = height;  // (all that BACKWARD::render reads)
     RenderBwdArgs ra[MAX_VIEWS];
     int nr = 0;
     for (int v = 0; v < V; v++) {
@@ -1330,8 +1184,8 @@ int gsr_backward_render_views(int V, int P, const int* R, const float* backgroun
         if (R[v] < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
         if (R[v] == 0) continue;
         if (!geom_buffers[v] || !binning_buffers[v]) return fail(GSR_ERR_ALLOC, "null state buffer");
-        ra[nr++] = render_bwd_args(P, R[v], background, width, height, geom_buffers[v], binning_buffers[v],
-                                   image_buffers[v], dL_dpix[v], has_inv ? dL_invdepths[v] : nullptr);
+        const ViewState vs = {geom_buffers[v], image_buffers[v], binning_buffers[v], 0, nullptr, nullptr, nullptr};
+        ra[nr++] = render_bwd_args(sc, vs, R[v], background, dL_dpix[v], has_inv ? dL_invdepths[v] : nullptr);
     }
     if (no) {
         ProfScope ps_(PK_TILE_ORDER, (hipStream_t)stream);
@@ -1715,7 +1569,7 @@ int gsr_debug_depth_sort(const uint32_t* keys, int n, uint32_t* out_ids, char* w
     uint32_t* v0 = reinterpret_cast<uint32_t*>(workspace + q);
     uint32_t* k1 = reinterpret_cast<uint32_t*>(workspace + 2 * q);
     uint32_t* v1 = reinterpret_cast<uint32_t*>(workspace + 3 * q);
-    // the forward's call (forward_geometry_sort) without the rect gather
+    // the forward's call (forward_geometry) without the rect gather
     HIP_TRY(radix_sort(n, DEPTH_BITS, keys, nullptr, k0, v0, k1, v1, out_ids, nullptr, nullptr, workspace + 4 * q, s));
     if (!depth_force_wide()) {  // three passes: the range word says whether they sufficed (else four, as the forward)
         uint32_t rw[2] = {0u, 1u};

@@ -177,13 +177,8 @@ hipError_t launch_preprocess(const PreprocessArgs& a, hipStream_t s);
 constexpr int PREPROCESS_BATCH = 8;
 hipError_t launch_preprocess_views(const PreprocessArgs* a, int V, hipStream_t s);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* view, bool* present, hipStream_t s);
-// Inclusive scan of in[gather[i]] (gather may be null): one launch, chained chunks with decoupled
-// look-back over `status` (scan_status_words(n) u64 words, zero on entry: preprocess clears them).
-// The total goes to *total_out (pinned host memory is fine).
+// The u64 words of a scan's `status` (ScanJob)
 int scan_status_words(int n);
-// exclusive: exclusive sums instead; total_out may be null.
-hipError_t launch_inclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, int n, uint64_t* status,
-                                 uint32_t* total_out, hipStream_t s, bool exclusive = false);
 
 // Batched prefix launches (gsr_forward_views): up to VIEW_BATCH views per launch, view =
 // blockIdx.y, each with its own arrays and sizes (workgroups past a view's size exit at once).
@@ -196,13 +191,17 @@ struct ViewBatch {
     int n;
 };
 
-struct ScanJob {  // launch_inclusive_scan's arguments for one view
+// One view's scan of in[0..n): chained chunks with decoupled look-back over `status`
+// (scan_status_words(n) u64 words, zero on entry: preprocess clears them).  The total goes to
+// *total_out (pinned host memory is fine; may be null).
+struct ScanJob {
     const uint32_t* in;
     uint32_t* out;
     int n;
     uint64_t* status;
     uint32_t* total_out;
 };
+// inclusive sums, or exclusive ones: one launch per VIEW_BATCH views
 hipError_t launch_scan_batch(const ScanJob* jobs, int V, bool exclusive, hipStream_t s);
 
 struct SortJob {  // radix_sort's arguments for one view
@@ -281,7 +280,8 @@ struct RangesJob {
     const uint32_t* sorted_tiles;
     uint2* ranges;
 };
-// views with L == 0 get their ranges zeroed (no emission cleared them)
+// views with L == 0 get their ranges zeroed (no emission cleared them); the others' ranges must be
+// zero on entry (the fused tile sort's first pass clears them)
 hipError_t launch_tile_ranges_batch(const RangesJob* jobs, int V, int T, hipStream_t s);
 
 struct OrderJob {
@@ -312,8 +312,6 @@ hipError_t radix_sort(int n, int nbits, const uint32_t* keys_in, const uint2* pa
                       uint32_t* k1, uint32_t* v1, uint32_t* out_x, uint32_t* out_y, uint32_t* sorted_keys,
                       char* scratch, hipStream_t s, const uint2* rects = nullptr, uint2* sorted_rects = nullptr,
                       uint32_t* sorted_counts = nullptr, SortKind kind = SORT_DEPTH);
-// ranges must be zero on entry unless L == 0 (the fused tile sort's first pass clears them)
-hipError_t launch_tile_ranges(int L, const uint32_t* sorted_tiles, uint2* ranges, int T, hipStream_t s);
 hipError_t launch_debug_keys(int L, const uint32_t* sorted_tiles, const uint32_t* point_list, const uint32_t* dkeys,
                              uint64_t* keys, hipStream_t s);
 hipError_t launch_debug_keys_from_ranges(int T, const uint2* ranges, const uint32_t* point_list, const uint32_t* dkeys,
@@ -322,7 +320,6 @@ hipError_t launch_debug_keys_from_ranges(int T, const uint2* ranges, const uint3
 // Longest-first launch order of the T tiles: order[] = tiles by decreasing work, work = range length
 // (ranges != null, the forward) or work[] (the backward's per-tile largest n_contrib).
 hipError_t launch_tile_order(const uint2* ranges, const uint32_t* work, int T, uint32_t* order, hipStream_t s);
-hipError_t launch_render_fwd(const RenderFwdArgs& a, int T, hipStream_t s);
 hipError_t launch_render_bwd(const RenderBwdArgs& a, int T, hipStream_t s);
 // V views of one image size in one launch per VIEW_BATCH views (grid.y = view); render_bwd: every
 // view with dL_invdepths, or none

@@ -536,18 +536,6 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* view, b
 
 int scan_status_words(int n) { return (n + SCAN_ITEMS - 1) / SCAN_ITEMS + 1; }  // + the ticket
 
-hipError_t launch_inclusive_scan(const uint32_t* in, const uint32_t* gather, uint32_t* out, int n, uint64_t* status,
-                                 uint32_t* total_out, hipStream_t s, bool exclusive)
-{
-    if (n <= 0) return hipSuccess;
-    const int nb = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
-    ViewBatch<ScanKArgs> B;
-    B.n = 1;
-    B.v[0] = {in, gather, n, nb, status, out, total_out};
-    hipLaunchKernelGGL(scan_lookback_kernel, dim3(nb), dim3(256), 0, s, B, exclusive);
-    return hipGetLastError();
-}
-
 hipError_t launch_scan_batch(const ScanJob* jobs, int V, bool exclusive, hipStream_t s)
 {
     for (int v0 = 0; v0 < V; v0 += VIEW_BATCH) {

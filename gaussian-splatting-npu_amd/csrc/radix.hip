@@ -1511,12 +1511,6 @@ hipError_t launch_debug_keys_from_ranges(int T, const uint2* ranges, const uint3
     return hipGetLastError();
 }
 
-hipError_t launch_tile_ranges(int L, const uint32_t* sorted_tiles, uint2* ranges, int T, hipStream_t s)
-{
-    const RangesJob j = {L, sorted_tiles, ranges};
-    return launch_tile_ranges_batch(&j, 1, T, s);
-}
-
 hipError_t launch_debug_keys(int L, const uint32_t* sorted_tiles, const uint32_t* point_list, const uint32_t* dkeys,
                              uint64_t* keys, hipStream_t s)
 {

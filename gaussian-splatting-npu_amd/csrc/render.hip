@@ -1008,8 +1008,6 @@ hipError_t launch_render_fwd_batch(const RenderFwdArgs* a, int V, int T, hipStre
     return hipSuccess;
 }
 
-hipError_t launch_render_fwd(const RenderFwdArgs& a, int T, hipStream_t s) { return launch_render_fwd_batch(&a, 1, T, s); }
-
 hipError_t launch_render_bwd_batch(const RenderBwdArgs* a, int V, int T, hipStream_t s)
 {
     if (T <= 0) return hipSuccess;

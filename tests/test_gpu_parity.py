@@ -482,3 +482,61 @@ def test_parameter_gradients_share_one_buffer():
     assert flat.numel() == sum(p.numel() for p in params.values())
     torch.testing.assert_close(flat, multiview.grad_bucket(params), rtol=0, atol=0)
 
+
+
+def _prefix_mode_outputs(case, cams):
+    """Forward and backward of `case` through GaussianRasterizer (first without, then with a binning
+    hint) and through a MultiViewRasterizer batch over `cams`: every output and gradient, by name."""
+    dgr = _dgr()
+    gc, gi = case["grad_color"].to(DEV), case["grad_invdepth"].to(DEV)
+    out = {}
+
+    def keep(tag, color, radii, inv, means2D, t, L):
+        torch.cuda.synchronize()
+        out.update({f"{tag}/color": color.detach(), f"{tag}/radii": radii, f"{tag}/invdepth": inv.detach(),
+                    f"{tag}/num_rendered": torch.tensor(L), f"{tag}/d_means2D": means2D.grad})
+        out.update({f"{tag}/d_{k}": v.grad for k, v in t.items()})
+
+    for tag in ("no_hint", "hint"):
+        if tag == "no_hint":
+            dgr._C._binning_hint.clear()  # gsr_forward_prealloc_dc leaves the view to gsr_forward_render
+        t, kw = _inputs(case, "sh_scales")
+        means2D = torch.zeros_like(t["means3D"], requires_grad=True)
+        color, radii, inv = dgr.GaussianRasterizer(_settings(case))(means2D=means2D, **kw)
+        L = dgr._C._binning_hint[t["means3D"].device]
+        torch.autograd.backward([color, inv], [gc, gi])
+        keep(tag, color, radii, inv, means2D, t, L)
+    t, kw = _inputs(case, "sh_scales")
+    V, P = len(cams), t["means3D"].shape[0]
+    means2D = torch.zeros((V, P, 3), device=DEV, requires_grad=True)
+    color, radii, inv = dgr.MultiViewRasterizer([_settings(dict(case, cam=c)) for c in cams])(means2D=means2D, **kw)
+    L = dgr._C._binning_hint_views[t["means3D"].device]
+    torch.autograd.backward([color, inv], [torch.stack([gc] * V), torch.stack([gi] * V)])
+    keep("views", color, radii, inv, means2D, t, L)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("P,H,W", [(1001, 256, 256),    # packed rects, ranges from the difference array
+                                   (3000, 256, 4096)])  # 256 tile columns: not packable, sorted tile ids
+def test_prefix_stream_modes_bit_identical(P, H, W):
+    """gsr_set_prefix_stream 1 (prefix stream + auxiliary stream), 0 (caller's stream only) and 2
+    (auxiliary stream only) change where the binning prefix is enqueued, never a result: images,
+    inverse depths, radii, num_rendered and every gradient of the single-view forwards
+    (gsr_forward_prealloc_dc alone, and followed by gsr_forward_render) and of a 2-view batch are
+    bit-identical across the modes."""
+    import synthetic
+    lib = _dgr()._C.lib
+    case = common.make_case(P=P, H=H, W=W)
+    cams = [synthetic.Camera(W, H, view=v) for v in range(2)]
+    res = {}
+    try:
+        for mode in (1, 0, 2):
+            assert lib.gsr_set_prefix_stream(mode) == 0
+            res[mode] = _prefix_mode_outputs(case, cams)
+    finally:
+        assert lib.gsr_set_prefix_stream(1) == 0
+    assert res[1]["hint/num_rendered"] > 0 and (res[1]["views/num_rendered"] > 0).all()
+    for mode in (0, 2):
+        assert res[mode].keys() == res[1].keys()
+        for k, ref in res[1].items():
+            assert np.array_equal(res[mode][k], ref), f"mode {mode}: {k} differs from mode 1"
