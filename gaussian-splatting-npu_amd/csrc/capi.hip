@@ -1421,6 +1421,39 @@ int gsr_densification_stats(int V, int P, const float* viewspace_grads, const in
     return GSR_OK;
 }
 
+// ---- parameter activations (activations.hip) ----
+int gsr_activate_forward(int P, const float* scaling, const float* rotation, const float* opacity, float* scales,
+                         float* rotations, float* opacities, gsr_stream_t stream)
+{
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (P == 0) return GSR_OK;
+    if (!scaling || !rotation || !opacity || !scales || !rotations || !opacities)
+        return fail(GSR_ERR_INVALID, "null pointer");
+    const ActivateFwdArgs a = {P, scaling, rotation, opacity, scales, rotations, opacities};
+    HIP_TRY(launch_activate_fwd(a, (hipStream_t)stream));
+    return GSR_OK;
+}
+
+int gsr_activate_backward(int P, const float* scales, const float* rotation, const float* opacities,
+                          const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
+                          float* dL_dscaling, float* dL_drotation, float* dL_dopacity, int accumulate_mask,
+                          gsr_stream_t stream)
+{
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (accumulate_mask & ~7) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
+    if (P == 0) return GSR_OK;
+    // a group runs when both its incoming gradient and its destination are given
+    const bool s = dL_dscales && dL_dscaling, r = dL_drotations && dL_drotation, o = dL_dopacities && dL_dopacity;
+    if (s && !scales) return fail(GSR_ERR_INVALID, "null pointer (scales)");
+    if (r && !rotation) return fail(GSR_ERR_INVALID, "null pointer (rotation)");
+    if (o && !opacities) return fail(GSR_ERR_INVALID, "null pointer (opacities)");
+    const ActivateBwdArgs a = {P, scales, rotation, opacities, s ? dL_dscales : nullptr, r ? dL_drotations : nullptr,
+                               o ? dL_dopacities : nullptr, s ? dL_dscaling : nullptr, r ? dL_drotation : nullptr,
+                               o ? dL_dopacity : nullptr, (uint32_t)accumulate_mask};
+    HIP_TRY(launch_activate_bwd(a, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 // ---- densify_and_prune (densify.hip) ----
 size_t gsr_densify_workspace_size(int P) { return densify_workspace_bytes(P); }
 

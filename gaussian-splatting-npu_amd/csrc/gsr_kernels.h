@@ -368,6 +368,37 @@ struct DensifyStatsArgs {
 };
 hipError_t launch_densify_stats(const DensifyStatsArgs& a, hipStream_t s);
 
+// parameter activations (activations.hip): scales = exp(scaling), opacities = sigmoid(opacity),
+// rotations = rotation / max(|rotation|_2, 1e-12), all (P,3) / (P,) / (P,4) contiguous, one launch.
+struct ActivateFwdArgs {
+    int P;
+    const float* scaling;
+    const float* rotation;
+    const float* opacity;
+    float* scales;
+    float* rotations;
+    float* opacities;
+};
+// bit set = that destination of the backward is added to instead of overwritten
+enum ActAccBits : uint32_t { ACT_ACC_SCALING = 1u, ACT_ACC_ROTATION = 2u, ACT_ACC_OPACITY = 4u };
+// the chain rule of the three activations from the saved outputs (scales, opacities) and the raw
+// quaternion; a group whose incoming gradient is null is skipped (its destination is not touched)
+struct ActivateBwdArgs {
+    int P;
+    const float* scales;
+    const float* rotation;
+    const float* opacities;
+    const float* dL_dscales;
+    const float* dL_drotations;
+    const float* dL_dopacities;
+    float* dL_dscaling;
+    float* dL_drotation;
+    float* dL_dopacity;
+    uint32_t acc;  // ACT_ACC_* bits
+};
+hipError_t launch_activate_fwd(const ActivateFwdArgs& a, hipStream_t s);
+hipError_t launch_activate_bwd(const ActivateBwdArgs& a, hipStream_t s);
+
 // densify_and_prune (densify.hip): the plan decides every source row's fate (one wave scans
 // DENSIFY_ROWS_PER_WAVE rows, four waves per workgroup) and leaves, in `workspace`, the source rows of
 // the output rows in output order; the apply writes every output element of every group once.

@@ -65,6 +65,8 @@ def _load(path=LIB_PATH):
     lib.gsr_adam_update.argtypes = [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _i, _vp]
     lib.gsr_adam_update_multi.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _vp]
     lib.gsr_densification_stats.argtypes = [_i, _i, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp]
+    lib.gsr_activate_forward.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.gsr_activate_backward.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]
     lib.gsr_densify_workspace_size.argtypes = [_i]
     lib.gsr_densify_workspace_size.restype = _sz
     lib.gsr_densify_rows_per_workgroup.argtypes = []
@@ -687,6 +689,92 @@ def densification_stats(viewspace_grads, radii, max_radii2D, accum, denom, visib
         _check(lib.gsr_densification_stats(
             V, P, grads.data_ptr(), radii.data_ptr(), max_radii2D.data_ptr(), accum.data_ptr(), rows[0],
             denom.data_ptr(), rows[1], visible_count.data_ptr() if visible_count is not None else None, _stream(dev)))
+
+
+def _act_check(name, t, P, cols):
+    """One array of the activation calls: float32, contiguous, (P, cols) -- (P, 1) or (P,) for
+    cols == 1."""
+    shapes = ((P, 1), (P,)) if cols == 1 else ((P, cols),)
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) not in shapes:
+        want = " or ".join(str(s) for s in shapes)
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name} must have shape {want}, got {got}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+
+
+def _act_device(named):
+    """The one GPU every (name, tensor) of `named` is on (checked after the arrays themselves, so a
+    wrong shape or dtype is reported as such wherever the tensor lives)."""
+    dev = None
+    for name, t in named:
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{name} must be on the GPU (HIP), got a tensor on {t.device}. There is no CPU path.")
+        if dev is not None and t.device != dev:
+            raise RuntimeError(f"{name} must be on {dev}, got {t.device}")
+        dev = t.device
+    return dev
+
+
+def activate_forward(scaling, rotation, opacity):
+    """gsr_activate_forward: (exp(scaling), normalize(rotation), sigmoid(opacity)) -- GaussianModel's
+    get_scaling / get_rotation / get_opacity (gaussian_model.py:102-135) -- in one launch.  scaling
+    (P,3), rotation (P,4), opacity (P,1) or (P,): contiguous float32 on one GPU.  Returns fresh
+    contiguous tensors shaped as the inputs."""
+    if not isinstance(scaling, torch.Tensor) or scaling.dim() != 2 or scaling.size(1) != 3:
+        raise RuntimeError("scaling must have shape (num_points, 3)")
+    P = scaling.size(0)
+    named = (("scaling", scaling, 3), ("rotation", rotation, 4), ("opacity", opacity, 1))
+    for name, t, cols in named:
+        _act_check(name, t, P, cols)
+    dev = _act_device([(name, t) for name, t, _ in named])
+    scales, rotations, opacities = torch.empty_like(scaling), torch.empty_like(rotation), torch.empty_like(opacity)
+    if P != 0:
+        with torch.cuda.device(dev):
+            _check(lib.gsr_activate_forward(P, scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
+                                            scales.data_ptr(), rotations.data_ptr(), opacities.data_ptr(),
+                                            _stream(dev)))
+    return scales, rotations, opacities
+
+
+# accumulate_mask of activate_backward: bit of each group
+ACT_ACC_BITS = {"scaling": 1, "rotation": 2, "opacity": 4}
+
+
+def activate_backward(scales, rotation, opacities, dL_dscales, dL_drotations, dL_dopacities, dL_dscaling,
+                      dL_drotation, dL_dopacity, accumulate_mask=0):
+    """gsr_activate_backward: the backward of activate_forward from its outputs `scales` and
+    `opacities` and the raw `rotation`.  A group (scaling, rotation, opacity) whose incoming gradient
+    or destination is None is skipped; the destinations are written in place -- overwritten, or added
+    to where the group's ACT_ACC_BITS bit of accumulate_mask is set.  Every tensor given: contiguous
+    float32 on one GPU, (P,3) / (P,4) / (P,1) or (P,); destinations may be views at any float offset."""
+    groups = (("scales", scales, "dL_dscales", dL_dscales, "dL_dscaling", dL_dscaling, 3),
+              ("rotation", rotation, "dL_drotations", dL_drotations, "dL_drotation", dL_drotation, 4),
+              ("opacities", opacities, "dL_dopacities", dL_dopacities, "dL_dopacity", dL_dopacity, 1))
+    accumulate_mask = int(accumulate_mask)
+    if accumulate_mask & ~7:
+        raise RuntimeError(f"accumulate_mask has unknown bits: {accumulate_mask}")
+    given = [t for g in groups for t in (g[1], g[3], g[5]) if isinstance(t, torch.Tensor)]
+    if not given:
+        return
+    P = given[0].size(0) if given[0].dim() else -1
+    named, ptrs = [], [None] * 9
+    for j, (n_in, t_in, n_g, t_g, n_d, t_d, cols) in enumerate(groups):
+        if t_g is None or t_d is None:
+            continue
+        for k, (name, t) in enumerate(((n_in, t_in), (n_g, t_g), (n_d, t_d))):
+            _act_check(name, t, P, cols)
+            named.append((name, t))
+            ptrs[3 * k + j] = t.data_ptr()
+    if not named:
+        return
+    dev = _act_device(named)
+    if P == 0:
+        return
+    with torch.cuda.device(dev):
+        _check(lib.gsr_activate_backward(P, *ptrs, accumulate_mask, _stream(dev)))
 
 
 def densify_rows_per_workgroup():

@@ -22,7 +22,7 @@ from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "SparseGaussianAdam",
            "accumulate_grads_in_place", "deferred_backward", "MultiViewRasterizer", "rasterize_views",
-           "grad_chunk_hook"]
+           "grad_chunk_hook", "fused_activations"]
 
 _state = threading.local()
 
@@ -376,6 +376,66 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_dc = None
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                 grad_rotations, grad_cov3Ds_precomp, None, grad_dc, None)
+
+
+def fused_activations(scaling, rotation, opacity):
+    """(scales, rotations, opacities) = (exp(scaling), normalize(rotation), sigmoid(opacity)):
+    GaussianModel.get_scaling / get_rotation / get_opacity (gaussian_model.py:102-135) as ONE HIP
+    launch forward and one backward (gsr_activate_forward / gsr_activate_backward) in place of the
+    torch chain's five and ten.  scaling (P,3), rotation (P,4), opacity (P,1) or (P,): contiguous
+    float32 on one GPU; the outputs are fresh contiguous tensors shaped as the inputs.
+    Differentiable once.  A call made inside accumulate_grads_in_place() adds the gradient of a
+    leaf input with an existing ``.grad`` into that ``.grad`` in the backward kernel (as the
+    rasterizer does for its leaf inputs) instead of returning it for autograd to add."""
+    return _FusedActivations.apply(scaling, rotation, opacity)
+
+
+class _FusedActivations(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scaling, rotation, opacity):
+        scales, rotations, opacities = _C.activate_forward(scaling, rotation, opacity)
+        # in-place accumulation (accumulate_grads_in_place): decided here, the targets re-checked
+        # by the backward (_accumulation_target), as _RasterizeGaussians does it
+        ctx.acc_inputs = (scaling, rotation, opacity) if getattr(_state, "accumulate", False) else None
+        ctx.set_materialize_grads(False)
+        # the backward of exp and sigmoid reads their outputs, that of normalize the raw quaternion
+        ctx.save_for_backward(scales, rotation, opacities)
+        return scales, rotations, opacities
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_scales, grad_rotations, grad_opacities):
+        scales, rotation, opacities = ctx.saved_tensors
+        shapes = (scales.shape, rotation.shape, opacities.shape)
+        gin, dst, out, mask = [None] * 3, [None] * 3, [None] * 3, 0
+        for j, g in enumerate((grad_scales, grad_rotations, grad_opacities)):
+            if g is None or not ctx.needs_input_grad[j]:
+                continue
+            gin[j] = g.contiguous()
+            target = _accumulation_target(ctx.acc_inputs[j]) if ctx.acc_inputs is not None else None
+            if target is not None:
+                dst[j] = target
+                mask |= 1 << j
+            else:
+                dst[j] = out[j] = torch.empty(shapes[j], dtype=torch.float32, device=g.device)
+        if all(g is None for g in gin):
+            return None, None, None
+        dev = rotation.device
+        if ctx.acc_inputs is not None:
+            stream = torch.cuda.current_stream(dev)
+            fence = _acc_fence.get(dev)
+            if mask and fence is not None:
+                stream.wait_event(fence)
+            for j in range(3):
+                if mask >> j & 1:
+                    dst[j].record_stream(stream)  # may have been allocated on another view's stream
+        _C.activate_backward(scales, rotation, opacities, gin[0], gin[1], gin[2], dst[0], dst[1], dst[2],
+                             accumulate_mask=mask)
+        if ctx.acc_inputs is not None:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            _acc_fence[dev] = ev
+        return out[0], out[1], out[2]
 
 
 class GaussianRasterizer(nn.Module):

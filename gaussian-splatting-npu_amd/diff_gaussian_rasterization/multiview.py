@@ -366,13 +366,23 @@ class DataParallelTrainer:
     and one apply launch sequence instead of the chain of appends and mask selections.  Same
     decisions, copied values and generator state; a split child's xyz and scaling are computed in
     the kernel and agree with the torch chain to fp32 rounding.
+
+    `fused_activations=True` (opt-in, GPU parameters; the default keeps the torch chain and its
+    bits): `activations()` computes exp(scaling), sigmoid(opacity) and normalize(rotation) with ONE
+    dgr.fused_activations call -- one HIP launch forward and one backward instead of the torch
+    chain's five and ten.  `render` / `render_views` make that call inside
+    accumulate_grads_in_place(), so the backward kernel adds the three raw gradients straight into
+    the flat buffer (the arithmetic of autograd's AccumulateGrad, without its three passes).  The
+    values agree with the torch chain to fp32 rounding.
     """
 
     def __init__(self, raw, lr=None, optimizer="sparse_adam", lambda_dssim=0.2, bg=None, group=None, batched=True,
                  seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False,
-                 fused_densify=False):
+                 fused_densify=False, fused_activations=False):
         import diff_gaussian_rasterization as dgr
         self._dgr = dgr
+        # exp / sigmoid / normalize of the raw parameters as one dgr.fused_activations call (off: torch)
+        self.fused_activations = fused_activations
         # densify_and_prune as the two HIP calls of fused_densify_and_prune (off: the torch chain)
         self.fused_densify = fused_densify
         # the L1 + D-SSIM loss of a rank's views as one fused_l1_ssim_loss call and the
@@ -452,11 +462,24 @@ class DataParallelTrainer:
         self.stats = densification_stats(P, dev)
 
     def activations(self):
-        """GaussianModel.get_* (gaussian_model.py:102-135)."""
+        """GaussianModel.get_* (gaussian_model.py:102-135): the torch chain, or with
+        `fused_activations` one dgr.fused_activations call (GPU parameters only)."""
         p = self.params
+        if self.fused_activations:
+            scales, rotations, opacities = self._dgr.fused_activations(p["scaling"], p["rotation"], p["opacity"])
+            return {"means3D": p["xyz"], "dc": p["f_dc"], "shs": p["f_rest"], "opacities": opacities,
+                    "scales": scales, "rotations": rotations}
         return {"means3D": p["xyz"], "dc": p["f_dc"], "shs": p["f_rest"],
                 "opacities": torch.sigmoid(p["opacity"]), "scales": torch.exp(p["scaling"]),
                 "rotations": torch.nn.functional.normalize(p["rotation"])}
+
+    def _activations_in_place(self):
+        """activations() for a render: the fused call inside accumulate_grads_in_place(), so its
+        backward adds the raw gradients into the flat buffer itself."""
+        if not self.fused_activations:
+            return self.activations()
+        with self._dgr.accumulate_grads_in_place():
+            return self.activations()
 
     def zero_grad(self):
         self.flat.zero_()
@@ -471,7 +494,7 @@ class DataParallelTrainer:
     def render(self, settings, act=None, cam_index=None, clamp=True):
         """gaussian_renderer.render with separate_sh=True: (clamped image, screen-space points, radii,
         inverse depth).  clamp=False: the exposed image before the clamp."""
-        act = act or self.activations()
+        act = act or self._activations_in_place()
         means2D = torch.zeros_like(act["means3D"], requires_grad=True)
         means2D.retain_grad()
         img, radii, inv = self._dgr.GaussianRasterizer(settings)(
@@ -483,7 +506,7 @@ class DataParallelTrainer:
     def render_views(self, settings_list, act=None):
         """render() for a batch of views in one MultiViewRasterizer call: (images (V,3,H,W) before
         exposure and clamp, screen-space points (V,P,3), radii (V,P), inverse depths (V,1,H,W))."""
-        act = act or self.activations()
+        act = act or self._activations_in_place()
         means2D = torch.zeros((len(settings_list),) + tuple(act["means3D"].shape), dtype=act["means3D"].dtype,
                               device=act["means3D"].device, requires_grad=True)
         means2D.retain_grad()

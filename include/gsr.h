@@ -382,6 +382,37 @@ int gsr_densification_stats(int V, int P, const float* viewspace_grads, const in
                             float* accum, long accum_stride, float* denom, long denom_stride,
                             float* visible_count, gsr_stream_t stream);
 
+/* The parameter activations between the optimizer's raw tensors and the rasterizer
+ * (GaussianModel.get_scaling / get_rotation / get_opacity, gaussian_model.py:102-135) for P Gaussians in
+ * one launch.  For every Gaussian i, in fp32 without contraction:
+ *   scales[3i+k]    = expf(scaling[3i+k]);
+ *   opacities[i]    = 1 / (1 + expf(-opacity[i]));
+ *   n = sqrtf(sum_k q_k^2), d = fmaxf(n, 1e-12f), rotations[4i+k] = q_k / d,   q = rotation[4i ..]
+ * (torch.nn.functional.normalize's x / max(|x|_2, eps) with its default eps 1e-12).  All six arrays
+ * are device memory, contiguous, 4-byte aligned; no output may overlap an input or another output.
+ * P == 0: nothing is launched.  P < 0 or a NULL pointer: GSR_ERR_INVALID.  Asynchronous. */
+int gsr_activate_forward(int P, const float* scaling, const float* rotation, const float* opacity,
+                         float* scales, float* rotations, float* opacities, gsr_stream_t stream);
+
+/* The backward of gsr_activate_forward: the chain rule torch's autograd applies to the same three ops,
+ * from the forward's OUTPUTS scales and opacities and the raw quaternions `rotation`:
+ *   dL_dscaling[3i+k]  = dL_dscales[3i+k] * scales[3i+k];
+ *   dL_dopacity[i]     = dL_dopacities[i] * (1 - y) * y,  y = opacities[i];
+ *   n, d as above, r = q / d, m = (n >= 1e-12f):
+ *   dL_drotation[4i+k] = (g_k - m r_k (r . g)) / d,  g = dL_drotations[4i ..]
+ * (m is clamp_min's mask: a quaternion shorter than eps, the zero one included, gets g / eps).
+ * Group g (0 scaling, 1 rotation, 2 opacity) is skipped -- nothing of it is read or written -- when its
+ * incoming gradient or its destination is NULL.  Bit g of accumulate_mask selects `+=` for that
+ * group's destination (one fp32 add per element, the arithmetic of autograd's AccumulateGrad; the
+ * contract of gsr_backward_dc_acc); otherwise it is overwritten.  Destinations need only 4-byte
+ * alignment (views of a flat gradient buffer at any float offset) and must not overlap an input or
+ * each other.  P == 0: nothing is launched.  P < 0 or unknown mask bits: GSR_ERR_INVALID.
+ * Asynchronous; results are bitwise reproducible. */
+int gsr_activate_backward(int P, const float* scales, const float* rotation, const float* opacities,
+                          const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
+                          float* dL_dscaling, float* dL_drotation, float* dL_dopacity,
+                          int accumulate_mask, gsr_stream_t stream);
+
 /* GaussianModel.densify_and_prune (gaussian_model.py:402-469) in two calls: gsr_densify_plan decides
  * what becomes of each of the P Gaussians and returns the counts the caller needs to allocate the new
  * tensors and to draw the split's samples; gsr_densify_apply writes the new tensors.  For source row i:

@@ -35,7 +35,9 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          "photo_loss_bwd_kernel": "photo_loss_bwd", "densify_stats_kernel": "densify_stats",
          # densify_and_prune (multiview.fused_densify_and_prune)
          "densify_decide_kernel": "densify_plan", "densify_offsets_kernel": "densify_plan",
-         "densify_scatter_kernel": "densify_plan", "densify_apply_kernel": "densify_apply"}
+         "densify_scatter_kernel": "densify_plan", "densify_apply_kernel": "densify_apply",
+         # the parameter activations (diff_gaussian_rasterization.fused_activations)
+         "activate_fwd_kernel": "activate_fwd", "activate_bwd_kernel": "activate_bwd"}
 # the kernel bench.py --pmc-child launches between its warm-up and its counted steps
 MARKER = "spin_kernel"
 # operations made of several kernels (several dispatches per call)

@@ -14,6 +14,19 @@
           gradient buffer both share; "fused_call" is multiview.fused_densify_and_prune alone, which
           the GB/s figure refers to.  Thresholds are quantiles of the seed-0 data: about 5 % of the
           rows clone, 5 % split and 5 % are pruned (the fractions are recorded).
+  activations: exp(scaling), sigmoid(opacity), F.normalize(rotation) and torch.autograd.backward on the
+          three outputs with fixed random gradients   vs   fused_activations (activate_fwd_kernel +
+          activate_bwd_kernel) inside accumulate_grads_in_place() with the same backward.  The raw
+          parameters carry .grad views of one flat buffer on both sides, so the torch side ends in
+          three AccumulateGrad additions and the fused side adds in its kernel.  The byte model is
+          64 B per Gaussian forward (32 in, 32 out) and 128 B backward with accumulation (saved
+          outputs, raw quaternion and incoming gradients 64 in; destinations 32 in and 32 out).
+  iteration: bench.py's aux_train_iteration restated at its scale (one 1M-Gaussian view at
+          --width x --height, dc=, SparseGaussianAdam) in its torch form (torch activations, torch L1 +
+          fused_ssim) against the all-HIP form (fused_activations, fused_l1_ssim_loss with V = 1),
+          the optimizer step the same.  Wall clock: time.perf_counter() around synchronised groups of
+          --group iterations, the two sides alternating group by group -- the host's dispatch cost is
+          part of what is compared.  A report, not a gate.
 
 Defaults are the bench's flagship shape: 8 views, 1920x1080, 1M Gaussians, seed-0 data.  The two
 sides alternate call by call; every call is bracketed by device events and ends in a
@@ -32,6 +45,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-npu_amd"))
+
+
+LEGS = ("loss", "stats", "densify", "activations", "iteration")
 
 
 def timed(fn, torch):
@@ -69,14 +85,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--legs", default="loss,stats,densify", help="comma-separated: loss, stats, densify")
+    ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated: " + ", ".join(LEGS))
+    ap.add_argument("--group", type=int, default=10, help="iterations per timed group of the iteration leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_tail.json"))
     args = ap.parse_args()
     if args.warmup < 3 or args.reps < 20:
         ap.error("at least 3 warm-ups and 20 timed repetitions per side")
     legs = set(args.legs.split(","))
-    if not legs or legs - {"loss", "stats", "densify"}:
-        ap.error("--legs takes loss, stats and densify")
+    if not legs or legs - set(LEGS):
+        ap.error("--legs takes " + ", ".join(LEGS))
+    if args.group < 1:
+        ap.error("--group must be >= 1")
 
     import torch
     if not torch.cuda.is_available():
@@ -111,6 +130,10 @@ def main():
         loss_stats_legs(args, legs, result, side, torch, multiview, fused_l1_ssim_loss, fused_ssim, dev)
     if "densify" in legs:
         result["densify"] = densify_leg(args, side, torch, multiview, dev)
+    if "activations" in legs:
+        result["activations"] = activations_leg(args, side, torch, dev)
+    if "iteration" in legs:
+        result["iteration"] = iteration_leg(args, side, torch, fused_l1_ssim_loss, fused_ssim, dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
@@ -298,6 +321,154 @@ def densify_leg(args, side, torch, multiview, dev):
                        "fused_call: fused_densify_and_prune alone (plan, read-back, randn, allocation, apply)")
     res["agreement"] = agreement
     return res
+
+
+def activations_leg(args, side, torch, dev):
+    """The torch activation chain against fused_activations (see the module docstring)."""
+    import diff_gaussian_rasterization as dgr
+    F = torch.nn.functional
+    P = args.points
+    g = torch.Generator(device="cpu").manual_seed(0)
+    start = {"scaling": torch.log(0.003 + 0.02 * torch.rand((P, 3), generator=g)),
+             "rotation": torch.randn((P, 4), generator=g), "opacity": 2.0 * torch.randn((P, 1), generator=g)}
+    names = ("scaling", "rotation", "opacity")
+    gout = [torch.randn(start[k].shape, generator=g).to(dev) for k in names]
+    fill = torch.randn((8 * P,), generator=g).to(dev)  # what the gradient views hold before every comparison
+    raw, flat = {}, {}
+    for k in ("torch", "fused"):  # each side's leaves, their .grad views of that side's flat buffer
+        flat[k] = fill.clone()
+        raw[k], off = [], 0
+        for n in names:
+            t = start[n].to(dev).requires_grad_(True)
+            t.grad = flat[k][off:off + t.numel()].view_as(t)
+            off += t.numel()
+            raw[k].append(t)
+
+    def torch_chain():
+        s, r, o = raw["torch"]
+        torch.autograd.backward((torch.exp(s), F.normalize(r), torch.sigmoid(o)), gout)
+
+    def fused():
+        with dgr.accumulate_grads_in_place():
+            out = dgr.fused_activations(*raw["fused"])
+        torch.autograd.backward(out, gout)
+
+    # agreement on these inputs (before any timing): the outputs, and what one backward added
+    with torch.no_grad():
+        a = (torch.exp(raw["torch"][0]), F.normalize(raw["torch"][1]), torch.sigmoid(raw["torch"][2]))
+        b = dgr.fused_activations(*raw["fused"])
+    torch_chain()
+    fused()
+    torch.cuda.synchronize()
+    agreement = {}
+    for j, n in enumerate(("scales", "rotations", "opacities")):
+        agreement[n + "_max_abs_diff"] = float((a[j] - b[j]).abs().max())
+        agreement[n + "_max_rel_diff"] = float(((a[j] - b[j]).abs() / a[j].abs().clamp_min(1e-30)).max())
+    off = 0
+    for j, n in enumerate(names):
+        k = raw["torch"][j].numel()
+        da, db, before = flat["torch"][off:off + k], flat["fused"][off:off + k], fill[off:off + k]
+        agreement["dL_d" + n + "_max_abs_diff_over_max"] = float((da - db).abs().max() / (da - before).abs().max())
+        off += k
+    agreement["grads_stay_views_of_the_flat_buffer"] = all(
+        t.grad.data_ptr() == flat[k][sum(x.numel() for x in raw[k][:j]):].data_ptr()
+        for k in raw for j, t in enumerate(raw[k]))
+    del a, b
+    r = alternate({"torch": torch_chain, "fused": fused}, args.warmup, args.reps, args.rounds, torch)
+    res = side(r, (64 + 128) * P)
+    res["byte_model"] = "64 B/Gaussian forward (32 in, 32 out) + 128 B/Gaussian backward with accumulation (64 in, 32 in and out)"
+    res["agreement"] = agreement
+    return res
+
+
+def iteration_leg(args, side, torch, fused_l1_ssim_loss, fused_ssim, dev):
+    """bench.py's aux_train_iteration in its torch form and in the all-HIP form (see the module
+    docstring): ms per iteration, wall clock."""
+    import time
+
+    import diff_gaussian_rasterization as dgr
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import synthetic  # the bench's scene and camera
+    F = torch.nn.functional
+    P, H, W = args.points, args.height, args.width
+    scene = {k: v.to(dev) for k, v in synthetic.make_scene(P, seed=0).items()}
+    cam = synthetic.Camera(W, H, view=0)
+    s = dgr.GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=torch.zeros(3, device=dev),
+        scale_modifier=1.0, viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev),
+        sh_degree=3, campos=cam.camera_center.to(dev), prefiltered=False, debug=False, antialiasing=False)
+    rast = dgr.GaussianRasterizer(raster_settings=s)
+    lr = {"xyz": 1.6e-4, "f_dc": 2.5e-3, "f_rest": 2.5e-3 / 20, "opacity": 2.5e-2, "scaling": 5e-3, "rotation": 1e-3}
+
+    def make(fused):
+        sh = scene["shs"]
+        raw = {"xyz": scene["means3D"].clone(), "f_dc": sh[:, :1].contiguous(), "f_rest": sh[:, 1:].contiguous(),
+               "opacity": torch.logit(scene["opacities"]), "scaling": torch.log(scene["scales"]),
+               "rotation": scene["rotations"].clone()}
+        raw = {k: torch.nn.Parameter(v) for k, v in raw.items()}
+        opt = dgr.SparseGaussianAdam([{"params": [p], "lr": lr[k], "name": k} for k, p in raw.items()], lr=0.0,
+                                     eps=1e-15)
+
+        def render():
+            means2D = torch.zeros_like(raw["xyz"], requires_grad=True)
+            if fused:
+                scales, rotations, opacities = dgr.fused_activations(raw["scaling"], raw["rotation"], raw["opacity"])
+            else:
+                scales, rotations, opacities = (torch.exp(raw["scaling"]), F.normalize(raw["rotation"]),
+                                                torch.sigmoid(raw["opacity"]))
+            return rast(means3D=raw["xyz"], means2D=means2D, dc=raw["f_dc"], shs=raw["f_rest"], opacities=opacities,
+                        scales=scales, rotations=rotations)
+
+        def iteration(gt):
+            img, radii, _ = render()
+            if fused:
+                loss = fused_l1_ssim_loss(img[None], [gt], 0.2)[0]
+            else:
+                loss = 0.8 * (img - gt).abs().mean() + 0.2 * (1.0 - fused_ssim(img[None], gt[None]))
+            loss.backward()
+            opt.step(radii > 0, P)
+            opt.zero_grad(set_to_none=True)
+            return loss.detach()
+        return render, iteration, raw
+
+    sides = {"torch": make(False), "fused": make(True)}
+    with torch.no_grad():
+        g = torch.Generator(device="cpu").manual_seed(0)
+        gt = (sides["torch"][0]()[0] + 0.05 * torch.randn((3, H, W), generator=g).to(dev)).clamp(0, 1)
+    first = {k: float(sides[k][1](gt)) for k in sides}  # the first iteration: from equal parameters
+    for _ in range(max(0, args.warmup - 1)):
+        for k in sides:
+            sides[k][1](gt)
+
+    def group(k):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(args.group):
+            sides[k][1](gt)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) / args.group * 1e3
+    meds = {k: [] for k in sides}
+    for _ in range(args.rounds):
+        t = {k: [] for k in sides}
+        for _ in range(args.reps):
+            for k in sides:
+                t[k].append(group(k))
+        for k in sides:
+            meds[k].append(statistics.median(t[k]))
+    r = {k: (statistics.median(m), max(m) - min(m), m) for k, m in meds.items()}
+    out = {}
+    for k, (med, spread, rounds) in r.items():
+        out[k] = {"median_ms_per_iteration": med, "spread_ms": spread, "round_medians_ms": rounds}
+    out["fused_faster_beyond_spread"] = bool(r["torch"][0] - r["fused"][0] > max(r["torch"][1], r["fused"][1]))
+    out["speedup"] = r["torch"][0] / r["fused"][0]
+    out["gaussians"], out["resolution"], out["iterations_per_group"] = P, [W, H], args.group
+    out["timing"] = ("time.perf_counter() around synchronised groups of iterations, the sides alternating group "
+                     "by group; torch: torch activations, torch L1 + fused_ssim; fused: fused_activations, "
+                     "fused_l1_ssim_loss (V = 1); both: GaussianRasterizer with dc=, SparseGaussianAdam.step")
+    out["agreement"] = {"first_iteration_loss_torch": first["torch"], "first_iteration_loss_fused": first["fused"],
+                        "first_iteration_loss_abs_diff": abs(first["torch"] - first["fused"])}
+    return out
 
 
 def alternate_prepared(sides, warmup, reps, rounds, torch):
