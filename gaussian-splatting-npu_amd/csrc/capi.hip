@@ -1406,6 +1406,80 @@ int gsr_photo_loss_backward(int V, int C, int H, int W, float lambda_dssim, int 
     return GSR_OK;
 }
 
+// the view-loss entry points' shared argument checks (no HIP call); *empty: a zero size, nothing to do
+static int view_loss_args(int V, int C, int H, int W, float lambda_dssim, int clamp, const float* const* gt,
+                          const float* exposure, const float* const* alpha_mask, const float* invdepth,
+                          const float* const* invdepth_target, const float* const* depth_mask, float depth_weight,
+                          bool* empty, ViewLossArgs* out)
+{
+    const int rc = photo_loss_args(V, C, H, W, lambda_dssim, gt, empty, &out->pv);
+    if (rc) return rc;
+    if (!(depth_weight >= 0.f && depth_weight <= 3.402823466e38f))  // NaN and inf included
+        return fail(GSR_ERR_INVALID, "depth_weight must be finite and >= 0");
+    if (*empty) return GSR_OK;
+    *empty = true;
+    if ((size_t)H * W >= ((size_t)1 << 30)) return fail(GSR_ERR_INVALID, "H*W must be < 2^30");  // 32-bit byte offsets
+    if (exposure && C != 3) return fail(GSR_ERR_INVALID, "exposure needs C == 3");
+    if (invdepth_target && !invdepth) return fail(GSR_ERR_INVALID, "invdepth_target without invdepth");
+    if (depth_mask && !invdepth_target) return fail(GSR_ERR_INVALID, "depth_mask without invdepth_target");
+    for (int v = 0; v < MAX_VIEWS; v++) {
+        out->mask[v] = alpha_mask && v < V ? alpha_mask[v] : nullptr;
+        out->target[v] = invdepth_target && v < V ? invdepth_target[v] : nullptr;
+        out->dmask[v] = depth_mask && v < V ? depth_mask[v] : nullptr;
+    }
+    out->exposure = exposure;
+    out->invdepth = invdepth;
+    out->depth_weight = depth_weight;
+    out->clamp = clamp != 0;
+    *empty = false;
+    return GSR_OK;
+}
+
+size_t gsr_view_loss_workspace_size(int V, int C, int H, int W)
+{
+    return V > MAX_VIEWS ? 0 : view_loss_workspace_bytes(V, C, H, W);
+}
+
+int gsr_view_loss_forward(int V, int C, int H, int W, float lambda_dssim, int clamp, const float* img,
+                          const float* const* gt, const float* exposure, const float* const* alpha_mask,
+                          const float* invdepth, const float* const* invdepth_target,
+                          const float* const* depth_mask, float depth_weight, float* loss, float* dm_dmu1,
+                          float* dm_dsigma1_sq, float* dm_dsigma12, void* workspace, void* stream)
+{
+    ViewLossArgs a;
+    bool empty;
+    const int rc = view_loss_args(V, C, H, W, lambda_dssim, clamp, gt, exposure, alpha_mask, invdepth,
+                                  invdepth_target, depth_mask, depth_weight, &empty, &a);
+    if (rc || empty) return rc;
+    if (!img || !loss || !workspace) return fail(GSR_ERR_INVALID, "null pointer");
+    const bool train = dm_dmu1 && dm_dsigma1_sq && dm_dsigma12;
+    HIP_TRY(launch_view_loss_fwd(a, H, W, lambda_dssim, img, loss, train ? dm_dmu1 : nullptr,
+                                 train ? dm_dsigma1_sq : nullptr, train ? dm_dsigma12 : nullptr, workspace,
+                                 (hipStream_t)stream));
+    return GSR_OK;
+}
+
+int gsr_view_loss_backward(int V, int C, int H, int W, float lambda_dssim, int clamp, const float* img,
+                           const float* const* gt, const float* exposure, const float* const* alpha_mask,
+                           const float* invdepth, const float* const* invdepth_target,
+                           const float* const* depth_mask, float depth_weight, const float* dL_dloss,
+                           const float* dm_dmu1, const float* dm_dsigma1_sq, const float* dm_dsigma12, float* dL_draw,
+                           float* dL_dexposure, float* dL_dinvdepth, void* workspace, void* stream)
+{
+    ViewLossArgs a;
+    bool empty;
+    const int rc = view_loss_args(V, C, H, W, lambda_dssim, clamp, gt, exposure, alpha_mask, invdepth,
+                                  invdepth_target, depth_mask, depth_weight, &empty, &a);
+    if (rc || empty) return rc;
+    if (!img || !dL_dloss || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !dL_draw)
+        return fail(GSR_ERR_INVALID, "null pointer");
+    if (exposure && (!dL_dexposure || !workspace))
+        return fail(GSR_ERR_INVALID, "null pointer (exposure needs dL_dexposure and the workspace)");
+    HIP_TRY(launch_view_loss_bwd(a, H, W, lambda_dssim, img, dL_dloss, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_draw,
+                                 dL_dexposure, invdepth ? dL_dinvdepth : nullptr, workspace, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 // ---- densification statistics (densify_stats.hip) ----
 int gsr_densification_stats(int V, int P, const float* viewspace_grads, const int* radii, float* max_radii2D,
                             float* accum, long accum_stride, float* denom, long denom_stride,

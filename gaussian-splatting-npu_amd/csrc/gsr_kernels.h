@@ -352,6 +352,29 @@ hipError_t launch_photo_loss_bwd(const PhotoViews& views, int H, int W, float la
                                  const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
                                  hipStream_t s);
 
+// fused view loss (ssim.hip): train.py:112-141 for V views, from the raw rasterizer outputs --
+//   e_c = sum_k raw_k E[k, c] + E[c, 3] (exposure: (V,3,4), C = 3; null: e = raw),
+//   x_c = clamp(e_c, 0, 1) * mask_v (mask[v]: (H,W) or null),
+//   loss[v] = photo(x, gt_v) + depth_weight mean|(invdepth_v - target[v]) * dmask[v]| (views with a target).
+struct ViewLossArgs {
+    PhotoViews pv;
+    const float* mask[MAX_VIEWS];
+    const float* target[MAX_VIEWS];
+    const float* dmask[MAX_VIEWS];
+    const float* exposure;
+    const float* invdepth;  // (V,H,W); the depth term runs if this is set, depth_weight > 0 and a view has a target
+    float depth_weight;
+    int clamp;
+};
+// bytes of the workspace of either pass (per-tile partial sums in double)
+size_t view_loss_workspace_bytes(int V, int C, int H, int W);
+hipError_t launch_view_loss_fwd(const ViewLossArgs& a, int H, int W, float lambda, const float* img, float* loss,
+                                float* dA, float* dB, float* dC, void* workspace, hipStream_t s);
+// dexposure: (V,3,4), with a.exposure; dinv: (V,H,W) or null (zero-filled if the depth term does not run)
+hipError_t launch_view_loss_bwd(const ViewLossArgs& a, int H, int W, float lambda, const float* img,
+                                const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
+                                float* dexposure, float* dinv, void* workspace, hipStream_t s);
+
 // densification statistics of V views in one pass (densify_stats.hip): for every Gaussian i and every
 // view v in order with radii[v, i] > 0: max_radii[i] = max(max_radii[i], radii[v, i]),
 // accum[i] += |grads[v, i, 0:2]|, denom[i] += 1, visible_count[i] += 1 (if given).  accum / denom are

@@ -537,6 +537,531 @@ __global__ void __launch_bounds__(256) photo_loss_bwd_kernel(SsGrid g, PhotoView
     }
 }
 
+// ---- fused view loss: exposure, alpha mask, L1 + D-SSIM and the inverse-depth L1 term (train.py:112-141) ----
+// Per view v (gsr_kernels.h ViewLossArgs):
+//   e_c = sum_k raw_k E[k, c] + E[c, 3],  x_c = clamp(e_c, 0, 1) * m,  loss = photo(x, gt) + w mean|(inv - t) dm|.
+// The exposure couples a pixel's three channels, so the unit of work is one 64x32 tile of a VIEW (of a
+// group of up to three channels; C = 3 is one group), not of a plane: the forward holds the tile's halo
+// of the three raw planes and the mask in registers (and one channel's ground truth, loaded a channel
+// ahead), and the channel loop inside the workgroup stages x_c from them -- the raw planes are read once
+// and no exposed image goes to memory.  Each channel is then photo_loss_fwd_kernel's window pass; the tile's (sum SSIM, sum L1)
+// over its channels is one pair of doubles.  The backward walks the same tiles: per channel the window
+// over the three partial planes gives dL/dx_c, g_c = m pass_c dL/dx_c, and the tile accumulates
+// dL/draw_k = sum_c E[k, c] g_c in registers (one store per raw plane) and the 12 sums of dL/dE, which
+// leave as 12 doubles per tile.  The inverse-depth term rides in both launches as leading tiles that
+// skip the window (one double per tile forward, dL/dinv stored directly backward).  Small reduce kernels
+// add each view's partials in an order that depends on the shape alone: no atomics anywhere.
+struct VlTile {
+    int v, c0, nc;  // the view; first channel and channel count (<= 3) of the tile's channel group
+    int x0, y0;
+    size_t plane0;  // offset of channel c0 of view v in the contiguous (V, C, H, W) arrays
+};
+
+__device__ __forceinline__ VlTile vl_tile(const SsGrid& g, int C, int groups, int t)
+{
+    const int x = t % g.tx, r = t / g.tx, y = r % g.ty, z = r / g.ty;
+    const int v = z / groups, c0 = 3 * (z - v * groups);
+    return {v, c0, C - c0 < 3 ? C - c0 : 3, x * SS_TW, y * SS_TH, ((size_t)v * C + c0) * g.H * g.W};
+}
+
+// Column c of a view's exposure: e_c = k[0] raw_0 + k[1] raw_1 + k[2] raw_2 + off (uniform: scalar loads).
+// Without an exposure: the unit column, so that dL/draw_c = g_c below; e_c itself is then raw_c, selected.
+struct VlColumn {
+    float k[3], off;
+};
+
+__device__ __forceinline__ VlColumn vl_column(const float* exposure, int v, int c)
+{
+    if (!exposure) return {{c == 0 ? 1.f : 0.f, c == 1 ? 1.f : 0.f, c == 2 ? 1.f : 0.f}, 0.f};
+    const float* E = exposure + v * 12;
+    return {{E[c], E[4 + c], E[8 + c]}, E[4 * c + 3]};
+}
+
+__device__ __forceinline__ float vl_pick(int c, float a0, float a1, float a2) { return c == 0 ? a0 : (c == 1 ? a1 : a2); }
+
+// the same expression in both passes: the backward's clamp mask is the forward's
+__device__ __forceinline__ float vl_expose(bool exposed, const VlColumn& E, int c, float r0, float r1, float r2)
+{
+    return exposed ? ((r0 * E.k[0] + r1 * E.k[1]) + r2 * E.k[2]) + E.off : vl_pick(c, r0, r1, r2);
+}
+
+// A plane's element at a 32-bit BYTE offset (H W < 2^30, checked by the callers): with a uniform base
+// this is one load with a scalar base and one offset register, shared by every plane of the tile --
+// 64-bit addresses per plane and element are what would not fit the register budget here.
+__device__ __forceinline__ float vl_ld(const float* plane, uint32_t byte_off)
+{
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(plane) + byte_off);
+}
+
+__device__ __forceinline__ void vl_st(float* plane, uint32_t byte_off, float x)
+{
+    *reinterpret_cast<float*>(reinterpret_cast<char*>(plane) + byte_off) = x;
+}
+
+// byte offset in its plane of halo element j of this thread for the tile at (x0, y0); outside the image
+// or the 74 columns: 0 (a valid address) and *in = false
+__device__ __forceinline__ uint32_t vl_halo_off(const SsGrid& g, int tid, int x0, int y0, int j, bool* in)
+{
+    const int i = tid + j * 256;
+    const int r = i / SS_LS, c = i - r * SS_LS;
+    const int y = y0 - SS_R + r, x = x0 - SS_R + c;
+    *in = i < SS_STAGE && c < SS_HW && y >= 0 && y < g.H && x >= 0 && x < g.W;
+    return *in ? 4u * ((uint32_t)y * (uint32_t)g.W + (uint32_t)x) : 0u;
+}
+
+// threadIdx.x, opaque to the optimiser: what is derived from it (13 halo rows and columns per thread) is
+// recomputed per tile in a few instructions instead of living in 26 registers across the whole kernel
+__device__ __forceinline__ int vl_tid()
+{
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    return tid;
+}
+
+// This thread's share of one view tile's halo: the raw planes and the mask, which stay for the tile's
+// channels, and the ground truth of ONE channel, reloaded per channel (one tile ahead like the rest).
+struct VlHalo {
+    float raw[3][SS_STAGE_IT], m[SS_STAGE_IT], gt[SS_STAGE_IT];
+    uint32_t outside;  // bit j: element j lies outside
+
+    __device__ __forceinline__ void load_view(const SsGrid& g, const ViewLossArgs& a, const float* img, const VlTile& t)
+    {
+        const size_t hw = (size_t)g.H * g.W;
+        const float* mp = a.mask[t.v];
+        const float* rp[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) rp[k] = img + t.plane0 + (k < t.nc ? k : 0) * hw;  // a short group re-reads
+        outside = 0;
+        const int tid = vl_tid();
+#pragma unroll
+        for (int j = 0; j < SS_STAGE_IT; j++) {
+            bool in;
+            const uint32_t o = vl_halo_off(g, tid, t.x0, t.y0, j, &in);
+            outside |= (in ? 0u : 1u) << j;
+#pragma unroll
+            for (int k = 0; k < 3; k++) raw[k][j] = vl_ld(rp[k], o);
+            m[j] = mp ? vl_ld(mp, o) : 1.f;
+        }
+    }
+    __device__ __forceinline__ void load_gt(const SsGrid& g, const ViewLossArgs& a, const VlTile& t, int c)
+    {
+        const float* gp = a.pv.gt[t.v] + (size_t)(t.c0 + c) * g.H * g.W;
+        const int tid = vl_tid();
+#pragma unroll
+        for (int j = 0; j < SS_STAGE_IT; j++) {
+            bool in;
+            gt[j] = vl_ld(gp, vl_halo_off(g, tid, t.x0, t.y0, j, &in));
+        }
+    }
+};
+
+// ... and of the backward's three partial planes of one channel
+struct VlHalo3 {
+    float v[3][SS_STAGE_IT];
+    uint32_t outside;
+
+    __device__ __forceinline__ void load(const float* dA, const float* dB, const float* dC, const SsGrid& g, int x0,
+                                         int y0)
+    {
+        outside = 0;
+        const int tid = vl_tid();
+#pragma unroll
+        for (int j = 0; j < SS_STAGE_IT; j++) {
+            bool in;
+            const uint32_t o = vl_halo_off(g, tid, x0, y0, j, &in);
+            outside |= (in ? 0u : 1u) << j;
+            v[0][j] = vl_ld(dA, o);
+            v[1][j] = vl_ld(dB, o);
+            v[2][j] = vl_ld(dC, o);
+        }
+    }
+    __device__ __forceinline__ float get(int k, int j) const { return (outside >> j) & 1 ? 0.f : v[k][j]; }
+};
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+view_loss_fwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, float C1, float C2, SsimWeights wt,
+                     const float* img, float* dA, float* dB, float* dC, double2* partial, double* dpartial)
+{
+    __shared__ float s1[SS_STAGE], s2[SS_STAGE];
+    __shared__ f2 hs[5][SS_HH][32];  // horizontal pass per column pair: x, y, xx, yy, xy
+    __shared__ double red[4][2];
+    const int p = threadIdx.x & 31, q = threadIdx.x >> 5;
+    const size_t hw = (size_t)g.H * g.W;
+    int t = blockIdx.x;
+    // the inverse-depth tiles (tile t of view t / (tx ty)): no window, one double each
+    for (; t < depth_tiles; t += gridDim.x) {
+        const int tx0 = (t % g.tx) * SS_TW, r = t / g.tx, ty0 = (r % g.ty) * SS_TH, v = r / g.ty;
+        const float* tg = a.target[v];
+        float d8 = 0.f;
+        if (tg) {
+            const float* dm = a.dmask[v];
+            const float* inv = a.invdepth + (size_t)v * hw;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int y = ty0 + 4 * q + i, x = tx0 + p + 32 * h;
+                    if (y >= g.H || x >= g.W) continue;
+                    const size_t o = (size_t)y * g.W + x;
+                    const float d = inv[o] - tg[o];
+                    d8 += fabsf(dm ? d * dm[o] : d);
+                }
+            }
+        }
+        const double sum = wave_sum((double)d8);
+        __syncthreads();  // the previous tile is done with red
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0) dpartial[t] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    }
+    if (t >= g.ntiles) return;  // uniform over the workgroup
+    VlHalo halo;
+    {
+        const VlTile n = vl_tile(g, a.pv.C, groups, t - depth_tiles);
+        halo.load_view(g, a, img, n);
+        halo.load_gt(g, a, n, 0);
+    }
+    for (; t < g.ntiles; t += gridDim.x) {
+        const VlTile cur = vl_tile(g, a.pv.C, groups, t - depth_tiles);
+        // this thread's 8 pixels of up to 3 channels (float: 24 terms of at most 1; the sums over threads
+        // and tiles are double)
+        float ssim8 = 0.f, l18 = 0.f;
+        for (int c = 0; c < cur.nc; c++) {  // uniform
+            const VlColumn E = vl_column(a.exposure, cur.v, c);
+            __syncthreads();  // the previous channel is done with s1, s2, hs and red
+#pragma unroll
+            for (int j = 0; j < SS_STAGE_IT; j++) {
+                const int i = threadIdx.x + j * 256;
+                if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+                const bool out = (halo.outside >> j) & 1;
+                const float e = vl_expose(a.exposure != nullptr, E, c, halo.raw[0][j], halo.raw[1][j], halo.raw[2][j]);
+                s1[i] = out ? 0.f : (a.clamp ? clamp01(e) : e) * halo.m[j];
+                s2[i] = out ? 0.f : halo.gt[j];
+            }
+            // the next channel's ground truth, or the next tile
+            if (c + 1 < cur.nc) {
+                halo.load_gt(g, a, cur, c + 1);
+            } else if (t + (int)gridDim.x < g.ntiles) {
+                const VlTile n = vl_tile(g, a.pv.C, groups, t + gridDim.x - depth_tiles);
+                halo.load_view(g, a, img, n);
+                halo.load_gt(g, a, n, 0);
+            }
+            __syncthreads();
+            for (int r = q; r < SS_HH; r += 8) {
+                f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
+                const float* r1 = s1 + r * SS_LS + p;
+                const float* r2 = s2 + r * SS_LS + p;
+#pragma unroll
+                for (int k = 0; k < 11; k++) {
+                    const f2 xa = {r1[k], r1[k + 32]}, xb = {r2[k], r2[k + 32]};
+                    const float w = wt.w[k];
+                    mx = pk_fma(w, xa, mx);
+                    my = pk_fma(w, xb, my);
+                    mxx = pk_fma(w, xa * xa, mxx);
+                    myy = pk_fma(w, xb * xb, myy);
+                    mxy = pk_fma(w, xa * xb, mxy);
+                }
+                hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
+            }
+            __syncthreads();
+            f2 m4[4][5];
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int k = 0; k < 5; k++) m4[i][k] = f2{0.f, 0.f};
+#pragma unroll
+            for (int rr = 0; rr < 14; rr++) {
+                f2 v[5];
+#pragma unroll
+                for (int k = 0; k < 5; k++) v[k] = hs[k][4 * q + rr][p];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int tap = rr - i;
+                    if (tap < 0 || tap > 10) continue;
+#pragma unroll
+                    for (int k = 0; k < 5; k++) m4[i][k] = pk_fma(wt.w[tap], v[k], m4[i][k]);
+                }
+            }
+            // (the pixels' coordinates and offsets recomputed per channel, not kept across the window passes)
+            const int et = vl_tid(), ep = et & 31, eq = et >> 5;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int y = cur.y0 + 4 * eq + i;
+                if (y >= g.H) break;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const int x = cur.x0 + ep + 32 * h;
+                    if (x >= g.W) continue;
+                    const float mu1 = m4[i][0][h], mu2 = m4[i][1][h];
+                    const float s11 = m4[i][2][h] - mu1 * mu1, s22 = m4[i][3][h] - mu2 * mu2;
+                    const float s12 = m4[i][4][h] - mu1 * mu2;
+                    const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
+                    const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
+                    const float inv = 1.f / (Cc * D);
+                    const float val = A * B * inv;
+                    const int ci = (4 * eq + i + SS_R) * SS_LS + ep + 32 * h + SS_R;  // the pixel itself in the halo
+                    ssim8 += val;
+                    l18 += fabsf(s1[ci] - s2[ci]);
+                    if (dA) {
+                        const size_t pl = cur.plane0 + c * hw;
+                        const uint32_t o = 4u * ((uint32_t)y * (uint32_t)g.W + (uint32_t)x);
+                        const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
+                        const float f_s11 = -val * Cc * inv;
+                        const float f_s12 = 2.f * A * inv;
+                        vl_st(dA + pl, o, f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12);
+                        vl_st(dB + pl, o, f_s11);
+                        vl_st(dC + pl, o, f_s12);
+                    }
+                }
+            }
+        }
+        const double sum_ssim = wave_sum((double)ssim8), sum_l1 = wave_sum((double)l18);
+        if ((threadIdx.x & 63) == 0) {
+            red[threadIdx.x >> 6][0] = sum_ssim;
+            red[threadIdx.x >> 6][1] = sum_l1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partial[t - depth_tiles] = double2{((red[0][0] + red[1][0]) + red[2][0]) + red[3][0],
+                                               ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]};
+    }
+}
+
+// One workgroup per view: its photo tiles' pairs and its depth tiles' sums, each added in an order that
+// depends on nothing but the shape.  depth_scale = depth_weight / (H W); dpartial null: no depth term.
+__global__ void __launch_bounds__(256) view_loss_reduce_kernel(const double2* partial, int tiles_per_view,
+                                                               const double* dpartial, int depth_tiles_per_view,
+                                                               double inv_n, double lambda, double depth_scale,
+                                                               float* loss)
+{
+    __shared__ double red[4][3];
+    const double2* pv = partial + (size_t)blockIdx.x * tiles_per_view;
+    double sum_ssim = 0.0, sum_l1 = 0.0, sum_d = 0.0;
+    for (int k = threadIdx.x; k < tiles_per_view; k += 256) {
+        const double2 e = pv[k];
+        sum_ssim += e.x;
+        sum_l1 += e.y;
+    }
+    if (dpartial)
+        for (int k = threadIdx.x; k < depth_tiles_per_view; k += 256)
+            sum_d += dpartial[(size_t)blockIdx.x * depth_tiles_per_view + k];
+    sum_ssim = wave_sum(sum_ssim);
+    sum_l1 = wave_sum(sum_l1);
+    sum_d = wave_sum(sum_d);
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = sum_ssim;
+        red[threadIdx.x >> 6][1] = sum_l1;
+        red[threadIdx.x >> 6][2] = sum_d;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double ssim = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) * inv_n;
+        const double l1 = (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]) * inv_n;
+        const double depth = (((red[0][2] + red[1][2]) + red[2][2]) + red[3][2]) * depth_scale;
+        loss[blockIdx.x] = (float)((1.0 - lambda) * l1 + lambda * (1.0 - ssim) + depth);
+    }
+}
+
+// dL/dx_c = dloss[v] (k_ssim (w * A + 2 x w * B + gt w * C) + k_l1 sign(x - gt)) at the masked x (photo_loss_bwd_kernel's
+// expression), g_c = m pass_c dL/dx_c, dL/draw_k = sum_c E[k, c] g_c; per tile the sums over its pixels of
+// raw_k g_c (at 4 k + c) and g_c (at 4 c + 3) go to epartial.  Depth tiles store
+// dL/dinv = dloss[v] k_depth sign((inv - t) dm) dm, zero for a view without a target.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+view_loss_bwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, SsimWeights wt, float k_ssim, float k_l1,
+                     float k_depth, const float* img, const float* dloss, const float* dA, const float* dB,
+                     const float* dC, float* dimg, float* dinv, double* epartial)
+{
+    __shared__ float gs[3][SS_STAGE];  // A, B, C over the halo (zero outside)
+    __shared__ f2 hs[3][SS_HH][32];
+    __shared__ double red[4][12];
+    const int p = threadIdx.x & 31, q = threadIdx.x >> 5;
+    const size_t hw = (size_t)g.H * g.W;
+    int t = blockIdx.x;
+    for (; t < depth_tiles; t += gridDim.x) {
+        const int tx0 = (t % g.tx) * SS_TW, r = t / g.tx, ty0 = (r % g.ty) * SS_TH, v = r / g.ty;
+        const float* tg = a.target[v];
+        const float* dm = a.dmask[v];
+        const float* inv = a.invdepth + (size_t)v * hw;
+        const float gv = dloss[v] * k_depth;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int y = ty0 + 4 * q + i, x = tx0 + p + 32 * h;
+                if (y >= g.H || x >= g.W) continue;
+                const size_t o = (size_t)y * g.W + x;
+                float out = 0.f;
+                if (tg) {
+                    const float w = dm ? dm[o] : 1.f;
+                    const float d = (inv[o] - tg[o]) * w;
+                    out = gv * (float)((d > 0.f) - (d < 0.f)) * w;
+                }
+                dinv[(size_t)v * hw + o] = out;
+            }
+        }
+    }
+    if (t >= g.ntiles) return;  // uniform over the workgroup
+    VlHalo3 halo;
+    {
+        const VlTile n = vl_tile(g, a.pv.C, groups, t - depth_tiles);
+        halo.load(dA + n.plane0, dB + n.plane0, dC + n.plane0, g, n.x0, n.y0);
+    }
+    for (; t < g.ntiles; t += gridDim.x) {
+        const VlTile cur = vl_tile(g, a.pv.C, groups, t - depth_tiles);
+        const float gv = dloss[cur.v];
+        const float* gtv = a.pv.gt[cur.v] + (size_t)cur.c0 * hw;
+        const float* mp = a.mask[cur.v];
+        // this thread's output pixels: the raw channels and the mask (0 outside the image: nothing flows)
+        float rw[3][4][2], mk[4][2], draw[3][4][2];
+        uint32_t off[4][2];  // byte offsets in a plane; 0 outside the image
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int y = cur.y0 + 4 * q + j, x = cur.x0 + p + 32 * h;
+                const bool in = y < g.H && x < g.W;
+                off[j][h] = in ? 4u * ((uint32_t)y * (uint32_t)g.W + (uint32_t)x) : 0u;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    rw[k][j][h] = vl_ld(img + cur.plane0 + (k < cur.nc ? k : 0) * hw, off[j][h]);
+                    draw[k][j][h] = 0.f;
+                }
+                mk[j][h] = in ? (mp ? vl_ld(mp, off[j][h]) : 1.f) : 0.f;
+            }
+        }
+        for (int c = 0; c < cur.nc; c++) {  // uniform
+            const VlColumn E = vl_column(a.exposure, cur.v, c);
+            float gt8[4][2];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) gt8[j][h] = vl_ld(gtv + c * hw, off[j][h]);
+            }
+            __syncthreads();  // the previous channel is done with gs, hs and red
+#pragma unroll
+            for (int j = 0; j < SS_STAGE_IT; j++) {
+                const int i = threadIdx.x + j * 256;
+                if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+                gs[0][i] = halo.get(0, j);
+                gs[1][i] = halo.get(1, j);
+                gs[2][i] = halo.get(2, j);
+            }
+            // the next channel's planes, or the next tile's first
+            if (c + 1 < cur.nc) {
+                const size_t pl = cur.plane0 + (c + 1) * hw;
+                halo.load(dA + pl, dB + pl, dC + pl, g, cur.x0, cur.y0);
+            } else if (t + (int)gridDim.x < g.ntiles) {
+                const VlTile n = vl_tile(g, a.pv.C, groups, t + gridDim.x - depth_tiles);
+                halo.load(dA + n.plane0, dB + n.plane0, dC + n.plane0, g, n.x0, n.y0);
+            }
+            __syncthreads();
+            for (int r = q; r < SS_HH; r += 8) {
+                f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+                for (int k = 0; k < 11; k++) {
+#pragma unroll
+                    for (int n = 0; n < 3; n++) {
+                        const float* row = gs[n] + r * SS_LS + p;
+                        s[n] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[n]);
+                    }
+                }
+                hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
+            }
+            __syncthreads();
+            f2 s4[4][3];
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int n = 0; n < 3; n++) s4[i][n] = f2{0.f, 0.f};
+#pragma unroll
+            for (int rr = 0; rr < 14; rr++) {
+                f2 v[3];
+#pragma unroll
+                for (int n = 0; n < 3; n++) v[n] = hs[n][4 * q + rr][p];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int tap = rr - i;
+                    if (tap < 0 || tap > 10) continue;
+#pragma unroll
+                    for (int n = 0; n < 3; n++) s4[i][n] = pk_fma(wt.w[tap], v[n], s4[i][n]);
+                }
+            }
+            float es[4] ={0.f, 0.f, 0.f, 0.f};  // this thread's sums of raw_k g_c and of g_c
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const float m = mk[j][h], gt = gt8[j][h];
+                    const float e = vl_expose(a.exposure != nullptr, E, c, rw[0][j][h], rw[1][j][h], rw[2][j][h]);
+                    const bool pass = !a.clamp || (e >= 0.f && e <= 1.f);  // torch's clamp backward
+                    const float xv = (a.clamp ? clamp01(e) : e) * m;
+                    const float d = xv - gt;
+                    const float sgn = (float)((d > 0.f) - (d < 0.f));
+                    const float ssim = s4[j][0][h] + 2.f * xv * s4[j][1][h] + gt * s4[j][2][h];
+                    const float gc = pass ? m * (gv * (k_ssim * ssim + k_l1 * sgn)) : 0.f;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        draw[k][j][h] += E.k[k] * gc;
+                        es[k] += rw[k][j][h] * gc;
+                    }
+                    es[3] += gc;
+                }
+            }
+            if (a.exposure) {  // uniform; red is read after the channel loop
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const double s = wave_sum((double)es[k]);
+                    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k < 3 ? 4 * k + c : 4 * c + 3] = s;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int y = cur.y0 + 4 * q + j;
+            if (y >= g.H) break;
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int x = cur.x0 + p + 32 * h;
+                if (x >= g.W) continue;
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    if (k < cur.nc)
+                        vl_st(dimg + cur.plane0 + k * hw, off[j][h], draw[k][j][h]);
+            }
+        }
+        if (a.exposure) {  // uniform
+            __syncthreads();
+            if (threadIdx.x < 12)
+                epartial[(size_t)(t - depth_tiles) * 12 + threadIdx.x] =
+                    ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+        }
+    }
+}
+
+// One workgroup per view: dL/dE[v] (3x4) from its tiles' 12 sums, in an order that depends on the shape alone.
+__global__ void __launch_bounds__(256) view_loss_exposure_reduce_kernel(const double* epartial, int tiles_per_view,
+                                                                        float* dexposure)
+{
+    __shared__ double red[4][12];
+    const double* pv = epartial + (size_t)blockIdx.x * tiles_per_view * 12;
+    double s[12];
+#pragma unroll
+    for (int n = 0; n < 12; n++) s[n] = 0.0;
+    for (int k = threadIdx.x; k < tiles_per_view; k += 256) {
+#pragma unroll
+        for (int n = 0; n < 12; n++) s[n] += pv[(size_t)k * 12 + n];
+    }
+#pragma unroll
+    for (int n = 0; n < 12; n++) {
+        const double w = wave_sum(s[n]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][n] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < 12)
+        dexposure[blockIdx.x * 12 + threadIdx.x] =
+            (float)(((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]);
+}
+
 // The reference's window (utils/loss_utils.py:46-53): exp in double, stored as float32,
 // normalised in float32 (gauss / gauss.sum()).
 static SsimWeights ssim_weights()
@@ -647,6 +1172,85 @@ hipError_t launch_photo_loss_bwd(const PhotoViews& views, int H, int W, float la
     const double n = (double)C * H * W;
     hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, views, ssim_weights(), clamp ? 1 : 0,
                        (float)(-(double)lambda / n), (float)((1.0 - (double)lambda) / n), img, dloss, dA, dB, dC, dimg);
+    return hipGetLastError();
+}
+
+// ---- fused view loss ----
+// Workspace, in doubles per view and tile position (txy = tiles of one plane): the forward's (SSIM, L1)
+// pair per channel group followed by the depth sums, V groups txy pairs then V txy doubles; the
+// backward's 12 exposure-gradient sums (one channel group).
+struct VlShape {
+    int groups;      // channel groups of up to 3 per view
+    size_t txy;      // tile positions of a plane
+    bool depth;      // the inverse-depth term runs
+};
+
+static VlShape view_loss_shape(const ViewLossArgs& a, int H, int W)
+{
+    VlShape s = {(a.pv.C + 2) / 3, photo_tiles_per_view(1, H, W), false};
+    if (a.invdepth && a.depth_weight > 0.f)
+        for (int v = 0; v < a.pv.V; v++) s.depth = s.depth || a.target[v] != nullptr;
+    return s;
+}
+
+size_t view_loss_workspace_bytes(int V, int C, int H, int W)
+{
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    const size_t fwd = 2 * (size_t)((C + 2) / 3) + 1;
+    return (size_t)V * photo_tiles_per_view(1, H, W) * (fwd > 12 ? fwd : 12) * sizeof(double);
+}
+
+hipError_t launch_view_loss_fwd(const ViewLossArgs& a, int H, int W, float lambda, const float* img, float* loss,
+                                float* dA, float* dB, float* dC, void* workspace, hipStream_t s)
+{
+    const int V = a.pv.V, C = a.pv.C;
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
+    const VlShape sh = view_loss_shape(a, H, W);
+    if ((size_t)V * (sh.groups + 1) > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    SsGrid g;
+    int blocks;
+    hipError_t e = ssim_grid(V * (sh.groups + (sh.depth ? 1 : 0)), H, W, &g, &blocks);
+    if (e != hipSuccess) return e;
+    const bool train = dA && dB && dC;
+    double2* partial = static_cast<double2*>(workspace);
+    double* dpartial = static_cast<double*>(workspace) + 2 * (size_t)V * sh.groups * sh.txy;
+    hipLaunchKernelGGL(view_loss_fwd_kernel, dim3(blocks), dim3(256), 0, s, g, a, sh.groups,
+                       sh.depth ? (int)(V * sh.txy) : 0, (float)(0.01 * 0.01), (float)(0.03 * 0.03), ssim_weights(), img,
+                       train ? dA : nullptr, dB, dC, partial, dpartial);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(view_loss_reduce_kernel, dim3(V), dim3(256), 0, s, partial, (int)(sh.groups * sh.txy),
+                       sh.depth ? dpartial : nullptr, (int)sh.txy, 1.0 / ((double)C * H * W), (double)lambda,
+                       (double)a.depth_weight / ((double)H * W), loss);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_loss_bwd(const ViewLossArgs& a, int H, int W, float lambda, const float* img,
+                                const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
+                                float* dexposure, float* dinv, void* workspace, hipStream_t s)
+{
+    const int V = a.pv.V, C = a.pv.C;
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
+    const VlShape sh = view_loss_shape(a, H, W);
+    if ((size_t)V * (sh.groups + 1) > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    const bool depth = sh.depth && dinv;
+    if (dinv && !depth) {
+        const hipError_t z = hipMemsetAsync(dinv, 0, (size_t)V * H * W * sizeof(float), s);
+        if (z != hipSuccess) return z;
+    }
+    SsGrid g;
+    int blocks;
+    hipError_t e = ssim_grid(V * (sh.groups + (depth ? 1 : 0)), H, W, &g, &blocks);
+    if (e != hipSuccess) return e;
+    const double n = (double)C * H * W;
+    double* epartial = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(view_loss_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, a, sh.groups,
+                       depth ? (int)(V * sh.txy) : 0, ssim_weights(), (float)(-(double)lambda / n),
+                       (float)((1.0 - (double)lambda) / n), (float)((double)a.depth_weight / ((double)H * W)), img, dloss,
+                       dA, dB, dC, dimg, dinv, epartial);
+    e = hipGetLastError();
+    if (e != hipSuccess || !a.exposure) return e;
+    hipLaunchKernelGGL(view_loss_exposure_reduce_kernel, dim3(V), dim3(256), 0, s, epartial, (int)sh.txy, dexposure);
     return hipGetLastError();
 }
 

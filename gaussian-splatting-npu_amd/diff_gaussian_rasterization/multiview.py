@@ -361,6 +361,13 @@ class DataParallelTrainer:
     without host synchronisations.  Exposure and the inverse-depth term stay in torch; a batch
     with an alpha-mask view takes the torch loss (the mask follows the clamp).
 
+    `fused_view_loss=True` (opt-in; the default keeps the torch chain and its bits): ALL of
+    train.py:112-141 for a rank's views -- per-camera exposure, clamp, alpha mask, L1 + D-SSIM and
+    the inverse-depth L1 term -- is ONE fused_ssim.fused_view_loss call on the raw rasterizer
+    images and inverse depths, in the batched and in the per-view branch; there is no torch
+    fallback for masked batches.  It replaces the loss of `fused_tail` when both are set (the
+    statistics launch of `fused_tail` is independent of it).
+
     `fused_densify=True` (opt-in, GPU parameters; the default keeps the torch chain, its bits and
     its use of the random generator): `densify_and_prune` is `fused_densify_and_prune` -- one plan
     and one apply launch sequence instead of the chain of appends and mask selections.  Same
@@ -378,7 +385,7 @@ class DataParallelTrainer:
 
     def __init__(self, raw, lr=None, optimizer="sparse_adam", lambda_dssim=0.2, bg=None, group=None, batched=True,
                  seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False,
-                 fused_densify=False, fused_activations=False):
+                 fused_densify=False, fused_activations=False, fused_view_loss=False):
         import diff_gaussian_rasterization as dgr
         self._dgr = dgr
         # exp / sigmoid / normalize of the raw parameters as one dgr.fused_activations call (off: torch)
@@ -388,6 +395,9 @@ class DataParallelTrainer:
         # the L1 + D-SSIM loss of a rank's views as one fused_l1_ssim_loss call and the
         # densification statistics as one add_batch_stats launch (off: the torch chain per view)
         self.fused_tail = fused_tail
+        # exposure, clamp, alpha mask, L1 + D-SSIM and the inverse-depth term of a rank's views as one
+        # fused_view_loss call on the raw renders (off: the torch chain, or fused_tail's loss)
+        self.fused_view_loss = fused_view_loss
         # > 1 (sparse Adam, several ranks): the gradient all-reduce and the optimizer step pipelined
         # over this many Gaussian ranges (reduce_and_step) in iterations without densification
         self.pipeline_chunks = pipeline_chunks
@@ -549,6 +559,22 @@ class DataParallelTrainer:
         photo = fused_l1_ssim_loss(imgs, [v[1] for v in views], self.lambda_dssim, clamp=True)
         return [self._add_depth_loss(photo[j], invs[j], e, depth_weight) for j, e in enumerate(extras)]
 
+    def _fused_view_losses(self, imgs, invs, views, depth_weight):
+        """_expose + clamp + _view_loss of every view as ONE fused_view_loss call.  imgs (V,3,H,W)
+        and invs (V,1,H,W): the rasterizer's outputs, before exposure and clamp."""
+        from fused_ssim import fused_view_loss
+        extras = [v[2] if len(v) > 2 and v[2] is not None else {} for v in views]
+        exposure = None
+        if self.exposures is not None and any(e.get("cam") is not None for e in extras):
+            identity = torch.eye(3, 4, dtype=torch.float32, device=imgs.device)  # a view without a camera
+            exposure = torch.stack([identity if e.get("cam") is None else self.exposures[e["cam"]] for e in extras])
+        losses = fused_view_loss(
+            imgs, [v[1] for v in views], self.lambda_dssim, clamp=True, exposure=exposure,
+            alpha_mask=[e.get("alpha_mask") for e in extras], invdepth=invs,
+            invdepth_target=[e.get("invdepth") for e in extras], depth_mask=[e.get("depth_mask") for e in extras],
+            depth_weight=depth_weight)
+        return list(losses.unbind(0))
+
     def _track(self, means2D_grads, radii, track_stats):
         """The densification statistics and the visibility counts of V views: (V,P,3), (V,P)."""
         with torch.no_grad():
@@ -574,7 +600,10 @@ class DataParallelTrainer:
         if self.batched and len(views) > 1:
             with self._dgr.accumulate_grads_in_place():
                 imgs, means2D, radii, invs = self.render_views([v[0] for v in views])
-            losses = self._fused_losses(imgs, invs, views, depth_weight) if self.fused_tail else None
+            if self.fused_view_loss:
+                losses = self._fused_view_losses(imgs, invs, views, depth_weight)
+            else:
+                losses = self._fused_losses(imgs, invs, views, depth_weight) if self.fused_tail else None
             if losses is None:
                 losses = [self._view_loss(self._expose(imgs[j], cam_of(v)).clamp(0, 1), invs[j], v, depth_weight)
                           for j, v in enumerate(views)]
@@ -586,9 +615,12 @@ class DataParallelTrainer:
             # xyz, f_dc, f_rest enter the rasterizer as leaves whose .grad are views of the flat
             # buffer: the backward kernel adds into them directly (no separate accumulation pass)
             with self._dgr.accumulate_grads_in_place():
-                img, means2D, radii, inv = self.render(v[0], cam_index=cam_of(v), clamp=not self.fused_tail)
+                img, means2D, radii, inv = self.render(v[0], cam_index=None if self.fused_view_loss else cam_of(v),
+                                                       clamp=not (self.fused_tail or self.fused_view_loss))
             loss = None
-            if self.fused_tail:  # img: exposed, not yet clamped
+            if self.fused_view_loss:  # img: the raw render
+                loss = self._fused_view_losses(img[None], inv[None], [v], depth_weight)[0]
+            elif self.fused_tail:  # img: exposed, not yet clamped
                 fused = self._fused_losses(img[None], inv[None], [v], depth_weight, exposed=True)
                 if fused is None:  # an alpha mask: the torch chain on the clamped image
                     img = img.clamp(0, 1)

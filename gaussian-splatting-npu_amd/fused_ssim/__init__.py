@@ -8,6 +8,11 @@ gradient are computed by the HIP kernels behind include/fused_ssim.h; there is n
 fused_l1_ssim_loss(img, gt, lambda_dssim=0.2, clamp=False) -> the whole photometric loss of
 train.py:119-124, (1 - lambda) L1 + lambda (1 - SSIM), for one image or a batch of views in one
 forward and one backward kernel (not part of the reference's module: an opt-in extra).
+
+fused_view_loss(img, gt, lambda_dssim=0.2, clamp=True, exposure=None, alpha_mask=None, invdepth=None,
+invdepth_target=None, depth_mask=None, depth_weight=0.0) -> all of train.py:112-141 from the raw
+rasterizer outputs: per-camera exposure, clamp, alpha mask, that loss and the inverse-depth L1 term,
+differentiable in img, exposure and invdepth (an opt-in extra as well).
 """
 import ctypes
 
@@ -192,4 +197,184 @@ def fused_l1_ssim_loss(img, gt, lambda_dssim=0.2, clamp=False):
     gts = [g.detach().contiguous() for g in gts]
     train = torch.is_grad_enabled() and x.requires_grad
     loss = FusedL1SSIMLoss.apply(x.contiguous(), float(lambda_dssim), bool(clamp), train, *gts)
+    return loss[0] if single else loss
+
+
+# ---- the whole per-view loss, from the raw rasterizer outputs, in one forward and one backward ------
+_lib.gsr_view_loss_workspace_size.restype = _sz
+_lib.gsr_view_loss_workspace_size.argtypes = [_i, _i, _i, _i]
+_lib.gsr_view_loss_forward.restype = _i
+_lib.gsr_view_loss_forward.argtypes = [_i, _i, _i, _i, _f, _i] + [_vp] * 7 + [_f] + [_vp] * 6
+_lib.gsr_view_loss_backward.restype = _i
+_lib.gsr_view_loss_backward.argtypes = [_i, _i, _i, _i, _f, _i] + [_vp] * 7 + [_f] + [_vp] * 9
+
+
+def _optional_pointers(ts):
+    """A host array of device pointers with NULL for None; None (no array) if every entry is None."""
+    if all(t is None for t in ts):
+        return None
+    return (_vp * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class FusedViewLoss(torch.autograd.Function):
+    """(V,) losses of a contiguous float32 (V,C,H,W) batch of raw renders.  exposure: (V,3,4) or None;
+    invdepth: (V,H,W)-sized or None (None unless the depth term runs); `views`: the per-view lists
+    (gts, alpha masks, depth targets, depth masks) with None entries; `train`: keep the partial
+    planes for a backward."""
+
+    @staticmethod
+    def forward(ctx, img, exposure, invdepth, lambda_dssim, clamp, depth_weight, train, views):
+        V, C, H, W = img.shape
+        dev = img.device
+        x = img.detach()
+        E = None if exposure is None else exposure.detach()
+        inv = None if invdepth is None else invdepth.detach()
+        loss = torch.empty((V,), dtype=torch.float32, device=dev)
+        parts = [torch.empty_like(x) for _ in range(3)] if train else [None] * 3
+        gts, masks, targets, dmasks = views
+        with torch.cuda.device(dev):
+            ws = torch.empty((_lib.gsr_view_loss_workspace_size(V, C, H, W),), dtype=torch.uint8, device=dev)
+            _gsr._check(_lib.gsr_view_loss_forward(
+                V, C, H, W, lambda_dssim, int(clamp), x.data_ptr(), _gt_pointers(gts), _ptr(E),
+                _optional_pointers(masks), _ptr(inv), _optional_pointers(targets), _optional_pointers(dmasks),
+                depth_weight, loss.data_ptr(), *[_ptr(p) for p in parts], ws.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream))
+        if train:
+            ctx.save_for_backward(x, E, inv, *parts)
+            ctx.views = views  # constants: they carry no graph
+        ctx.cfg = (lambda_dssim, clamp, depth_weight, train)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lambda_dssim, clamp, depth_weight, train = ctx.cfg
+        if not train:
+            raise RuntimeError("fused_view_loss kept no state for a backward pass")
+        x, E, inv, dA, dB, dC = ctx.saved_tensors
+        gts, masks, targets, dmasks = ctx.views
+        V, C, H, W = x.shape
+        dev = x.device
+        g = dloss.detach().to(torch.float32).contiguous()  # stays on the device: the kernel reads it
+        grad = torch.empty_like(x)
+        dE = None if E is None else torch.empty_like(E)
+        dinv = None if inv is None else torch.empty_like(inv)
+        with torch.cuda.device(dev):
+            ws = torch.empty((_lib.gsr_view_loss_workspace_size(V, C, H, W),), dtype=torch.uint8, device=dev)
+            _gsr._check(_lib.gsr_view_loss_backward(
+                V, C, H, W, lambda_dssim, int(clamp), x.data_ptr(), _gt_pointers(gts), _ptr(E),
+                _optional_pointers(masks), _ptr(inv), _optional_pointers(targets), _optional_pointers(dmasks),
+                depth_weight, g.data_ptr(), dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), grad.data_ptr(), _ptr(dE),
+                _ptr(dinv), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return grad, dE, dinv, None, None, None, None, None
+
+
+def _per_view(name, t, V, H, W, single, dev):
+    """`t` -- None, one tensor for all views, or a sequence with None entries -- as a list of V
+    contiguous float32 (H W)-sized tensors or None."""
+    if t is None:
+        return [None] * V
+    if torch.is_tensor(t):
+        if single:
+            ts = [t]
+        elif t.dim() >= 3 and t.shape[0] == V:
+            ts = list(t.unbind(0))
+        else:
+            raise RuntimeError(f"{name} must have one (H, W) plane per view")
+    else:
+        ts = list(t)
+    if len(ts) != V:
+        raise RuntimeError(f"{V} views but {len(ts)} entries in {name}")
+    out = []
+    for e in ts:
+        if e is not None:
+            if not torch.is_tensor(e) or e.dim() < 2 or tuple(e.shape[-2:]) != (H, W) or e.numel() != H * W:
+                raise RuntimeError(f"every {name} entry must be None or one (H, W) plane of the image size")
+            if e.device != dev or e.dtype != torch.float32:
+                raise RuntimeError(f"{name} must be float32 on {dev}")
+            e = e.detach().contiguous()
+        out.append(e)
+    return out
+
+
+def fused_view_loss(img, gt, lambda_dssim=0.2, clamp=True, exposure=None, alpha_mask=None, invdepth=None,
+                    invdepth_target=None, depth_mask=None, depth_weight=0.0):
+    """train.py:112-141 for a batch of views, from the raw rasterizer outputs, in one forward and one
+    backward launch sequence (view_loss_fwd_kernel / view_loss_bwd_kernel):
+
+        e_c    = sum_k img_k E_v[k, c] + E_v[c, 3]          (exposure (V,3,4), 3 channels; None: e = img)
+        x_c    = clamp(e_c, 0, 1) * m_v                      (`clamp`; alpha_mask (1,H,W) per view; None: 1)
+        loss_v = (1 - lambda_dssim) mean|x - gt_v| + lambda_dssim (1 - mean SSIM(x, gt_v))
+                 + depth_weight mean|(invdepth_v - t_v) * dm_v|    (views with a target t_v only)
+
+    img: float32 (V,C,H,W) with 1 <= V <= 16, or (C,H,W) (then exposure is (3,4) and the per-view
+    inputs single tensors).  gt, alpha_mask, invdepth_target, depth_mask: one tensor for all views or
+    a sequence of V tensors, with None for a view that has none (gt: every view).  invdepth:
+    (V,1,H,W).  Returns the (V,) losses (0-dim for a 3-D img), differentiable in img, exposure and
+    invdepth (sign(0) = 0; the clamp passes the gradient for 0 <= e <= 1).  If no view has a depth
+    target, or depth_weight == 0, invdepth receives no gradient at all (None, not zeros), so the
+    rasterizer's backward skips its inverse-depth term.  With every optional input absent this is
+    fused_l1_ssim_loss, bit for bit.  GPU only; there is no CPU path."""
+    if img.device.type != "cuda":
+        raise RuntimeError(f"fused_view_loss runs on the GPU only (HIP); got a tensor on {img.device}")
+    if img.dim() not in (3, 4):
+        raise RuntimeError("img must be (V, C, H, W) or (C, H, W)")
+    if img.dtype != torch.float32:
+        raise RuntimeError(f"img must be float32, got {img.dtype}")
+    depth_weight = float(depth_weight)
+    if not 0.0 <= depth_weight < float("inf"):
+        raise RuntimeError(f"depth_weight must be finite and >= 0, got {depth_weight}")
+    single = img.dim() == 3
+    x = img[None] if single else img
+    V, C, H, W = x.shape
+    dev = x.device
+    if not 1 <= V <= MAX_VIEWS:
+        raise RuntimeError(f"fused_view_loss takes 1 to {MAX_VIEWS} views, got {V}")
+    if torch.is_tensor(gt) and gt.shape != img.shape:
+        raise RuntimeError("img and gt must have the same shape")
+    masks = _per_view("alpha_mask", alpha_mask, V, H, W, single, dev)
+    targets = _per_view("invdepth_target", invdepth_target, V, H, W, single, dev)
+    dmasks = _per_view("depth_mask", depth_mask, V, H, W, single, dev)
+    if invdepth is None:
+        if any(t is not None for t in targets):
+            raise RuntimeError("invdepth_target needs invdepth, the rendered inverse depth")
+    else:
+        if not torch.is_tensor(invdepth) or invdepth.dim() < 2 or tuple(invdepth.shape[-2:]) != (H, W) \
+                or invdepth.numel() != V * H * W:
+            raise RuntimeError("invdepth must be (V, 1, H, W), one plane of the image size per view")
+        if invdepth.device != dev or invdepth.dtype != torch.float32:
+            raise RuntimeError(f"invdepth must be float32 on {dev}")
+    if exposure is not None:
+        if not torch.is_tensor(exposure) or tuple(exposure.shape) != ((3, 4) if single else (V, 3, 4)):
+            raise RuntimeError("exposure must be (V, 3, 4), or (3, 4) for a 3-D img")
+        if C != 3:
+            raise RuntimeError(f"exposure needs a 3-channel img, got {C} channels")
+        if exposure.device != dev or exposure.dtype != torch.float32:
+            raise RuntimeError(f"exposure must be float32 on {dev}")
+    depth = invdepth is not None and depth_weight > 0 and any(t is not None for t in targets)
+    if exposure is None and not depth and all(m is None for m in masks):
+        return fused_l1_ssim_loss(img, gt, lambda_dssim, clamp)
+    gts = [gt] if single and torch.is_tensor(gt) else (list(gt.unbind(0)) if torch.is_tensor(gt) else list(gt))
+    if len(gts) != V:
+        raise RuntimeError(f"{V} views but {len(gts)} ground-truth images")
+    for g in gts:
+        if not torch.is_tensor(g) or g.shape != x.shape[1:]:
+            raise RuntimeError("every ground-truth image must have the shape of one view of img")
+        if g.device != dev or g.dtype != torch.float32:
+            raise RuntimeError(f"ground-truth images must be float32 on {dev}")
+    if x.numel() == 0:
+        raise RuntimeError("img is empty")
+    if H * W >= 2 ** 30:
+        raise RuntimeError("fused_view_loss takes images of fewer than 2^30 pixels")
+    gts = [g.detach().contiguous() for g in gts]
+    E = None if exposure is None else (exposure[None] if single else exposure).contiguous()
+    inv = invdepth.reshape(V, 1, H, W).contiguous() if depth else None
+    if not depth:
+        targets, dmasks = [None] * V, [None] * V
+    train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, E, inv))
+    loss = FusedViewLoss.apply(x.contiguous(), E, inv, float(lambda_dssim), bool(clamp), depth_weight, train,
+                               (gts, masks, targets, dmasks))
     return loss[0] if single else loss

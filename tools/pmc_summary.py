@@ -33,6 +33,8 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          # the fused training tail (tools/train_tail_bench.py)
          "photo_loss_fwd_kernel": "photo_loss_fwd", "photo_loss_reduce_kernel": "photo_loss_fwd",
          "photo_loss_bwd_kernel": "photo_loss_bwd", "densify_stats_kernel": "densify_stats",
+         "view_loss_fwd_kernel": "view_loss_fwd", "view_loss_reduce_kernel": "view_loss_fwd",
+         "view_loss_bwd_kernel": "view_loss_bwd", "view_loss_exposure_reduce_kernel": "view_loss_bwd",
          # densify_and_prune (multiview.fused_densify_and_prune)
          "densify_decide_kernel": "densify_plan", "densify_offsets_kernel": "densify_plan",
          "densify_scatter_kernel": "densify_plan", "densify_apply_kernel": "densify_apply",

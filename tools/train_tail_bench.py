@@ -5,6 +5,14 @@
   loss:   per view clamp, (img - gt).abs().mean(), fused_ssim, the scalar mix, and their backward
           (DataParallelTrainer._view_loss on the clamped image)   vs   one fused_l1_ssim_loss
           call (photo_loss_fwd_kernel + photo_loss_bwd_kernel) and its backward;
+  view_loss: what train.py:112-141 does per view with `train_test_exp` exposures, an alpha mask and a depth
+          target on every view -- DataParallelTrainer._expose, clamp, _view_loss (mask, L1, fused_ssim,
+          the inverse-depth L1 term) and their backward   vs   one fused_view_loss call on the raw
+          renders (DataParallelTrainer._fused_view_losses: view_loss_fwd_kernel + view_loss_bwd_kernel and
+          their small reductions) and its backward.  Gradients go to the image, the inverse depths and the
+          exposures on both sides.  The byte model is 42 floats per pixel and view: forward 3 raw, 3
+          ground-truth and the mask in, 9 partial planes out, and inverse depth, target and depth mask in;
+          backward the 9 planes, raw, ground truth and mask in, 3 out, and the depth term's 3 in, 1 out.
   stats:  V x multiview.add_view_stats (boolean-mask indexing, a host synchronisation each)
           vs   one multiview.add_batch_stats launch (densify_stats_kernel);
   densify: DataParallelTrainer.densify_and_prune as the torch chain (two appends and two mask
@@ -47,7 +55,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-npu_amd"))
 
 
-LEGS = ("loss", "stats", "densify", "activations", "iteration")
+LEGS = ("loss", "view_loss", "stats", "densify", "activations", "iteration")
 
 
 def timed(fn, torch):
@@ -128,6 +136,8 @@ def main():
         "timing": "device events around each call, synchronised; sides alternate call by call"})
     if legs & {"loss", "stats"}:
         loss_stats_legs(args, legs, result, side, torch, multiview, fused_l1_ssim_loss, fused_ssim, dev)
+    if "view_loss" in legs:
+        result["view_loss"] = view_loss_leg(args, side, torch, multiview, dev)
     if "densify" in legs:
         result["densify"] = densify_leg(args, side, torch, multiview, dev)
     if "activations" in legs:
@@ -204,6 +214,67 @@ def loss_stats_legs(args, legs, result, side, torch, multiview, fused_l1_ssim_lo
         stat = alternate({"torch": torch_stats, "fused": fused_stats}, args.warmup, args.reps, args.rounds, torch)
         # radii and (gx, gy) of every (view, Gaussian); accum, denom, max radius and count read and written
         result["stats"] = side(stat, V * P * 12 + P * 32)
+
+
+def view_loss_leg(args, side, torch, multiview, dev):
+    """The trainer's torch chain for exposure, clamp, mask, loss and depth term against fused_view_loss
+    (see the module docstring)."""
+    V, H, W, lam, weight = args.views, args.height, args.width, args.lambda_dssim, 0.5
+    g = torch.Generator(device="cpu").manual_seed(0)
+    img = (1.4 * torch.rand((V, 3, H, W), generator=g) - 0.2).to(dev).requires_grad_(True)
+    inv = (0.1 + torch.rand((V, 1, H, W), generator=g)).to(dev).requires_grad_(True)
+    exposures = torch.eye(3, 4)[None].repeat(V, 1, 1) + 0.05 * torch.randn((V, 3, 4), generator=g)
+    views = []
+    for j in range(V):  # separate tensors per view, as the trainer's
+        keep = torch.rand((1, H, W), generator=g) >= 0.3
+        extras = {"cam": j,
+                  "alpha_mask": (keep * (0.25 + 0.75 * torch.rand((1, H, W), generator=g))).to(dev),
+                  "invdepth": (0.1 + torch.rand((1, H, W), generator=g)).to(dev),
+                  "depth_mask": (torch.rand((1, H, W), generator=g) > 0.2).float().to(dev)}
+        views.append((None, torch.rand((3, H, W), generator=g).to(dev), extras))
+    names = multiview.TRAIN_GROUPS
+    tiny = {"xyz": torch.zeros((1, 3)), "f_dc": torch.zeros((1, 1, 3)), "f_rest": torch.zeros((1, 15, 3)),
+            "opacity": torch.zeros((1, 1)), "scaling": torch.zeros((1, 3)), "rotation": torch.ones((1, 4))}
+    tr = multiview.DataParallelTrainer({n: tiny[n].to(dev) for n in names}, lambda_dssim=lam, exposures=exposures)
+
+    def reset():
+        img.grad = None
+        inv.grad = None
+        tr.zero_grad()  # the exposure gradients live in the trainer's flat buffer
+
+    def torch_chain():
+        reset()
+        losses = [tr._view_loss(tr._expose(img[j], j).clamp(0, 1), inv[j], v, weight) for j, v in enumerate(views)]
+        torch.stack(losses).sum().backward()
+        return losses
+
+    def fused():
+        reset()
+        losses = tr._fused_view_losses(img, inv, views, weight)
+        torch.stack(losses).sum().backward()
+        return losses
+
+    # the two sides on these inputs (before any timing)
+    out = {}
+    for k, fn in (("torch", torch_chain), ("fused", fused)):
+        losses = torch.stack([l.detach() for l in fn()])
+        out[k] = (losses, img.grad.clone(), tr.exposures.grad.clone(), inv.grad.clone())
+
+    def rel(i):
+        return float((out["torch"][i] - out["fused"][i]).abs().max() / out["torch"][i].abs().max())
+    agreement = {"loss_max_abs_diff": float((out["torch"][0] - out["fused"][0]).abs().max()),
+                 "dL_draw_max_abs_diff_over_max": rel(1), "dL_dexposure_max_abs_diff_over_max": rel(2),
+                 "dL_dinvdepth_max_abs_diff_over_max": rel(3)}
+    del out
+    r = alternate({"torch": torch_chain, "fused": fused}, args.warmup, args.reps, args.rounds, torch)
+    res = side(r, 42 * 4 * V * H * W)
+    res["byte_model"] = ("per pixel and view, in floats: forward 3 raw + 3 gt + mask in, 9 partial planes out, "
+                         "inverse depth + target + depth mask in (19); backward 9 planes + 3 raw + 3 gt + mask in, "
+                         "3 out, inverse depth + target + depth mask in, 1 out (23)")
+    res["scene"] = "every view with an exposure, an alpha mask (about 30 % zero) and a depth target with a depth mask"
+    res["depth_weight"] = weight
+    res["agreement"] = agreement
+    return res
 
 
 def densify_leg(args, side, torch, multiview, dev):
