@@ -72,7 +72,8 @@ constexpr int PINNED_SLOT_WORDS = 16;
 int pinned(int slot, uint32_t** out)
 {
     if (!g_pinned) {
-        hipError_t e = hipHostMalloc((void**)&g_pinned, 4 * PINNED_SLOT_WORDS * MAX_VIEWS,
+        // (two more slots behind the views': gsr_union_plan's 1 + UNION_MAX_BOUNDS words)
+        hipError_t e = hipHostMalloc((void**)&g_pinned, 4 * PINNED_SLOT_WORDS * (MAX_VIEWS + 2),
                                      hipHostMallocMapped | hipHostMallocCoherent);
         if (e != hipSuccess) return fail_hip(e, __LINE__);
     }
@@ -1608,6 +1609,83 @@ int gsr_densify_apply(int P, int P_after, int n_split, int N, int n_groups, cons
     }
     HIP_TRY(launch_densify_apply(a, workspace, (hipStream_t)stream));
     return GSR_OK;
+}
+
+// ---- visibility-compacted gradient exchange (compact.hip) ----
+int gsr_union_rows_per_wave(void) { return UNION_ROWS_PER_WAVE; }
+
+size_t gsr_union_workspace_size(int P) { return union_workspace_bytes(P); }
+
+int gsr_visibility_pack(int P, const float* count, uint32_t* words, gsr_stream_t stream)
+{
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (P == 0) return GSR_OK;
+    if (!count || !words) return fail(GSR_ERR_INVALID, "null pointer");
+    HIP_TRY(launch_visibility_pack(P, count, words, (hipStream_t)stream));
+    return GSR_OK;
+}
+
+int gsr_union_plan(int P, int ranks, const uint32_t* words, int n_bounds, const int* bounds, char* workspace,
+                   uint32_t* rows, uint8_t* mask, int* U, int* bound_ranks, gsr_stream_t stream)
+{
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (ranks < 1) return fail(GSR_ERR_INVALID, "ranks must be >= 1");
+    if (n_bounds < 0 || n_bounds > UNION_MAX_BOUNDS) return fail(GSR_ERR_INVALID, "n_bounds must be in [0, 16]");
+    if (!U || (n_bounds > 0 && (!bounds || !bound_ranks))) return fail(GSR_ERR_INVALID, "null pointer");
+    for (int k = 0; k < n_bounds; k++)
+        if (bounds[k] < 0 || bounds[k] > P || (bounds[k] != P && bounds[k] % UNION_ROWS_PER_WAVE != 0))
+            return fail(GSR_ERR_INVALID, "a boundary must be P or a multiple of gsr_union_rows_per_wave() in [0, P]");
+    *U = 0;
+    for (int k = 0; k < n_bounds; k++) bound_ranks[k] = 0;
+    if (P == 0) return GSR_OK;
+    if (!words || !workspace || !rows) return fail(GSR_ERR_INVALID, "null pointer");
+    uint32_t* h;
+    int rc = pinned(MAX_VIEWS, &h);  // (the two slots behind the forward's and the densify plan's)
+    if (rc) return rc;
+    for (int k = 0; k <= n_bounds; k++) h[k] = L_PENDING;  // (every count is <= P < 2^31)
+    HIP_TRY(launch_union_plan(P, ranks, words, n_bounds, bounds, workspace, rows, mask, h, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int k = 0; k <= n_bounds; k++)
+        if (__atomic_load_n(&h[k], __ATOMIC_ACQUIRE) == L_PENDING)
+            return fail(GSR_ERR_HIP, "the plan did not publish its counts");
+    *U = (int)h[0];
+    for (int k = 0; k < n_bounds; k++) bound_ranks[k] = (int)h[1 + k];
+    return GSR_OK;
+}
+
+static int rows_move(bool scatter, int P, int U, int u0, int u1, int n_groups, const int* Ms, float* const* full,
+                     const uint32_t* rows, float* compact, gsr_stream_t stream)
+{
+    if (P < 0 || U < 0 || n_groups < 0) return fail(GSR_ERR_INVALID, "P, U and n_groups must be >= 0");
+    if (U > P) return fail(GSR_ERR_INVALID, "U must be <= P");
+    if (n_groups > ADAM_MAX_GROUPS) return fail(GSR_ERR_INVALID, "n_groups must be <= 8");
+    if (u0 < 0 || u1 > U || u0 > u1) return fail(GSR_ERR_INVALID, "window outside [0, U]");
+    if (P == 0 || U == 0 || u0 == u1 || n_groups == 0) return GSR_OK;
+    if (!Ms || !full || !rows || !compact) return fail(GSR_ERR_INVALID, "null pointer");
+    RowsMoveArgs a = {};
+    a.P = P; a.U = U; a.u0 = u0; a.u1 = u1; a.n_groups = n_groups;
+    a.rows = rows; a.compact = compact;
+    for (int g = 0; g < n_groups; g++) {
+        if (Ms[g] < 0) return fail(GSR_ERR_INVALID, "M must be >= 0");
+        if ((size_t)U * Ms[g] >= 0xFFFFFFF0ull) return fail(GSR_ERR_INVALID, "U*M must be < 2^32 - 16");
+        if (Ms[g] > 0 && !full[g]) return fail(GSR_ERR_INVALID, "null group pointer");
+        a.M[g] = Ms[g];
+        a.full[g] = full[g];
+    }
+    HIP_TRY(launch_rows_move(a, scatter, (hipStream_t)stream));
+    return GSR_OK;
+}
+
+int gsr_rows_gather(int P, int U, int u0, int u1, int n_groups, const int* Ms, const float* const* src,
+                    const uint32_t* rows, float* compact, gsr_stream_t stream)
+{
+    return rows_move(false, P, U, u0, u1, n_groups, Ms, const_cast<float* const*>(src), rows, compact, stream);
+}
+
+int gsr_rows_scatter(int P, int U, int u0, int u1, int n_groups, const int* Ms, float* const* dst,
+                     const uint32_t* rows, const float* compact, gsr_stream_t stream)
+{
+    return rows_move(true, P, U, u0, u1, n_groups, Ms, dst, rows, const_cast<float*>(compact), stream);
 }
 
 // ---- simple_knn.h ----

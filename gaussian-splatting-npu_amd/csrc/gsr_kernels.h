@@ -459,6 +459,29 @@ float densify_split_shrink(int N);  // a child's scale is its parent's divided b
 hipError_t launch_densify_plan(const DensifyPlanArgs& a, char* workspace, uint32_t* host_counts, hipStream_t s);
 hipError_t launch_densify_apply(const DensifyApplyArgs& a, const char* workspace, hipStream_t s);
 
+// visibility-compacted gradient exchange (compact.hip): the bit set of the Gaussians a rank's views saw,
+// the union of the ranks' sets as an ascending row list, and the move of those rows of every group
+// into and out of a compact buffer laid out [group][union row][column].
+constexpr int UNION_ROWS_PER_WAVE = 1024;  // one wave of the plan covers this many Gaussians (32 words)
+constexpr int UNION_MAX_BOUNDS = 16;
+// words: (P + 31) / 32; bit g & 31 of word g >> 5 = count[g] > 0, bits at or beyond P zero
+hipError_t launch_visibility_pack(int P, const float* count, uint32_t* words, hipStream_t s);
+size_t union_workspace_bytes(int P);
+// words: (ranks, (P + 31) / 32); rows: P words, [0, U) written; mask: P bytes or null; bounds: n_bounds
+// <= UNION_MAX_BOUNDS host ints, each a multiple of UNION_ROWS_PER_WAVE or P; host_out: 1 + n_bounds
+// words of pinned host memory (U, then the union rows below each boundary), valid once the stream has
+// been synchronised
+hipError_t launch_union_plan(int P, int ranks, const uint32_t* words, int n_bounds, const int* bounds,
+                             char* workspace, uint32_t* rows, uint8_t* mask, uint32_t* host_out, hipStream_t s);
+struct RowsMoveArgs {
+    int P, U, u0, u1, n_groups;  // the window [u0, u1) of the U union rows
+    int M[ADAM_MAX_GROUPS];      // floats per row (0: the group is skipped)
+    float* full[ADAM_MAX_GROUPS];  // (P, M[g]) (only read by the gather)
+    const uint32_t* rows;        // the plan's list
+    float* compact;              // U * sum(M) floats (only read by the scatter)
+};
+hipError_t launch_rows_move(const RowsMoveArgs& a, bool scatter, hipStream_t s);
+
 // distCUDA2 (knn.hip); host_bounds: 6 words of pinned host memory
 size_t knn_workspace_bytes(int P);
 hipError_t knn_dist2(int P, const float* pts, float* dist2, char* workspace, uint32_t* host_bounds, hipStream_t s);

@@ -74,6 +74,14 @@ def _load(path=LIB_PATH):
                                      ctypes.POINTER(_i), _vp]
     lib.gsr_densify_apply.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_i), _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp]
+    lib.gsr_union_rows_per_wave.argtypes = []
+    lib.gsr_union_workspace_size.argtypes = [_i]
+    lib.gsr_union_workspace_size.restype = _sz
+    lib.gsr_visibility_pack.argtypes = [_i, _vp, _vp, _vp]
+    lib.gsr_union_plan.argtypes = [_i, _i, _vp, _i, ctypes.POINTER(_i), _vp, _vp, _vp, ctypes.POINTER(_i),
+                                   ctypes.POINTER(_i), _vp]
+    lib.gsr_rows_gather.argtypes = [_i, _i, _i, _i, _i, ctypes.POINTER(_i), _vp, _vp, _vp, _vp]
+    lib.gsr_rows_scatter.argtypes = lib.gsr_rows_gather.argtypes
     lib.gsr_debug_sorted_keys.argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]
     lib.gsr_debug_depth_sort_workspace_size.argtypes = [_i]
     lib.gsr_debug_depth_sort_workspace_size.restype = _sz
@@ -856,6 +864,118 @@ def densify_apply(workspace, counts, N, names, src, src_state, dst, dst_state, s
         _check(lib.gsr_densify_apply(
             P, P_after, n_split, int(N), n, (_i * n)(*Ms), *role_idx, *[(_vp * n)(*c) for c in cols],
             samples.data_ptr() if n_split else None, workspace.data_ptr(), _stream(dev)))
+
+
+def union_rows_per_wave():
+    """Gaussians one wave of union_plan covers: its boundaries are multiples of this (or P)."""
+    return int(lib.gsr_union_rows_per_wave())
+
+
+def visibility_words(P):
+    """int32 words of one rank's visibility bits for P Gaussians."""
+    return (int(P) + 31) // 32
+
+
+def visibility_pack(count, out=None):
+    """gsr_visibility_pack: bit (g & 31) of word (g >> 5) = count[g] > 0 for the contiguous float32 (P,)
+    `count`; bits at or beyond P are zero.  Returns the int32 tensor of (P + 31) // 32 words (`out`, if
+    given).  Asynchronous."""
+    _require_gpu(count)
+    dev = count.device
+    if count.dtype != torch.float32 or count.dim() != 1 or not count.is_contiguous():
+        raise RuntimeError("count must be a contiguous float32 tensor of shape (num_points,)")
+    P = count.numel()
+    n = visibility_words(P)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=dev)
+    elif out.device != dev or out.dtype != torch.int32 or out.numel() != n or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous int32 tensor of {n} words on {dev}")
+    if P:
+        with torch.cuda.device(dev):
+            _check(lib.gsr_visibility_pack(P, count.data_ptr(), out.data_ptr(), _stream(dev)))
+    return out
+
+
+def union_plan(words, P, bounds=None, rows=None, mask=None, workspace=None):
+    """gsr_union_plan: the union of the ranks' visibility bits as an ascending row list.  words: int32
+    (ranks, (P + 31) // 32), contiguous, one visibility_pack row per rank.  bounds: up to 16 Gaussian
+    indices, each P or a multiple of union_rows_per_wave().  rows: an int32 (P,) tensor to write the
+    list into (allocated if None; only [0, U) is written).  mask: True for a fresh bool (P,) union
+    mask, a bool (P,) tensor to write it into, or None.  workspace: a uint8 tensor of
+    gsr_union_workspace_size(P) bytes to reuse, or None.  Returns (U, rows, mask, bound_ranks) with
+    bound_ranks[k] the number of union rows below bounds[k].  One stream synchronisation."""
+    _require_gpu(words)
+    dev = words.device
+    P = int(P)
+    n = visibility_words(P)
+    if words.dtype != torch.int32 or words.dim() != 2 or words.size(1) != n or not words.is_contiguous():
+        raise RuntimeError(f"words must be a contiguous int32 tensor of shape (ranks, {n})")
+    ranks = words.size(0)
+    if ranks < 1:
+        raise RuntimeError("ranks must be >= 1")
+    bounds = [int(b) for b in (bounds or [])]
+    if len(bounds) > 16:
+        raise RuntimeError("at most 16 boundaries")
+    if rows is None:
+        rows = torch.empty((P,), dtype=torch.int32, device=dev)
+    elif rows.device != dev or rows.dtype != torch.int32 or rows.numel() < P or not rows.is_contiguous():
+        raise RuntimeError(f"rows must be a contiguous int32 tensor of {P} elements on {dev}")
+    if mask is True:
+        mask = torch.empty((P,), dtype=torch.bool, device=dev)
+    elif mask is not None and (mask.device != dev or mask.dtype != torch.bool or mask.numel() != P
+                               or not mask.is_contiguous()):
+        raise RuntimeError(f"mask must be a contiguous bool tensor of {P} elements on {dev}")
+    need = int(lib.gsr_union_workspace_size(P))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.device != dev or workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise RuntimeError(f"workspace must be a uint8 tensor of {need} bytes on {dev}")
+    nb = len(bounds)
+    U, ranks_out = _i(0), (_i * max(nb, 1))()
+    with torch.cuda.device(dev):
+        _check(lib.gsr_union_plan(P, ranks, words.data_ptr() if P else None, nb, (_i * max(nb, 1))(*bounds),
+                                  workspace.data_ptr() if P else None, rows.data_ptr() if P else None,
+                                  mask.data_ptr() if mask is not None and P else None, ctypes.byref(U), ranks_out,
+                                  _stream(dev)))
+    return int(U.value), rows, mask, [int(ranks_out[k]) for k in range(nb)]
+
+
+def _rows_move(fn, name, tensors, rows, U, compact, window):
+    if not tensors:
+        raise RuntimeError(f"{name}: no tensors")
+    _require_gpu(tensors[0])
+    dev = tensors[0].device
+    P = tensors[0].size(0)
+    U = int(U)
+    Ms = []
+    for k, t in enumerate(tensors):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.size(0) != P:
+            raise RuntimeError(f"{name}: tensor {k} must be a contiguous float32 tensor of {P} rows on {dev}")
+        Ms.append(t.numel() // P if P else 0)
+    if len(tensors) > 8:
+        raise RuntimeError(f"{name}: at most 8 groups")
+    if rows.device != dev or rows.dtype != torch.int32 or rows.numel() < U or not rows.is_contiguous():
+        raise RuntimeError(f"{name}: rows must be union_plan's int32 list of at least U = {U} rows on {dev}")
+    total = U * sum(Ms)  # [group][union row][column]: multiview.compact_layout
+    if compact.device != dev or compact.dtype != torch.float32 or compact.numel() < total or not compact.is_contiguous():
+        raise RuntimeError(f"{name}: compact must be a contiguous float32 tensor of at least {total} elements on {dev}")
+    u0, u1 = (0, U) if window is None else (int(window[0]), int(window[1]))
+    n = len(tensors)
+    with torch.cuda.device(dev):
+        _check(fn(P, U, u0, u1, n, (_i * n)(*Ms), (_vp * n)(*[t.data_ptr() if t.numel() else None for t in tensors]),
+                  rows.data_ptr(), compact.data_ptr(), _stream(dev)))
+
+
+def rows_gather(tensors, rows, U, compact, window=None):
+    """gsr_rows_gather: the union rows rows[u0:u1] (window, default all U) of every (P, ...) float32
+    tensor into `compact` (layout: multiview.compact_layout), all tensors in one launch.  Asynchronous."""
+    _rows_move(lib.gsr_rows_gather, "rows_gather", tensors, rows, U, compact, window)
+
+
+def rows_scatter(tensors, rows, U, compact, window=None):
+    """gsr_rows_scatter: the inverse of rows_gather -- writes the window's union rows of every tensor
+    from `compact` and touches no other row.  Asynchronous."""
+    _rows_move(lib.gsr_rows_scatter, "rows_scatter", tensors, rows, U, compact, window)
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

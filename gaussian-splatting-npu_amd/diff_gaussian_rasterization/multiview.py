@@ -167,6 +167,104 @@ def allreduce_densification_stats(stats, group=None):
     return sums.numel() * sums.element_size() + mr.numel() * mr.element_size()
 
 
+# Union fraction U / P at and above which compact_allreduce leaves the exchange to the dense
+# collective: where the gather + scatter of the union rows costs what the rows left out save on the
+# links.  The copies are measured on one MI355X (0.47 ns per union row for both at
+# SH degree 3, 0.055 ms for pack + plan at 1M Gaussians; profiles/train_tail.json, `compact`); the link
+# rate is ASSUMED (330 GB/s bus rate at N = 8, ring factor 2 (N - 1) / N: 1.27 ns per dense row), no
+# multi-GPU timing exists.  Break-even 0.70 (0.699 and 0.711 in two runs), rounded down to a
+# multiple of 0.05 from the lower one.
+COMPACT_BELOW = 0.65
+
+
+def compact_layout(U, Ms):
+    """Where the groups of a compact buffer start: [group][union row][column], group k at
+    U * sum(Ms[:k]) floats; the last entry is the total U * sum(Ms).  Pure Python."""
+    off, at = [], 0
+    for M in Ms:
+        off.append(at)
+        at += int(U) * int(M)
+    return off + [at]
+
+
+class CompactBuffers:
+    """What compact_allreduce keeps between steps for P Gaussians on one device: the gathered word
+    rows, the union's row list and mask, the plan's workspace and the compact buffer (grown on
+    demand, never shrunk)."""
+
+    def __init__(self, P, ranks, device):
+        from . import _C
+        n = _C.visibility_words(P)
+        self.P, self.ranks = P, ranks
+        self.words = torch.zeros((ranks, n), dtype=torch.int32, device=device)
+        self.rows = torch.empty((P,), dtype=torch.int32, device=device)
+        self.mask = torch.empty((P,), dtype=torch.bool, device=device)
+        self.workspace = torch.empty((int(_C.lib.gsr_union_workspace_size(P)),), dtype=torch.uint8, device=device)
+        self.compact = torch.empty((0,), dtype=torch.float32, device=device)
+
+    def compact_for(self, n):
+        if self.compact.numel() < n:
+            self.compact = torch.empty((n,), dtype=torch.float32, device=self.compact.device)
+        return self.compact
+
+
+def _gather_words(buffers, visible_count, group):
+    """Packs this rank's visibility and all-gathers every rank's words into buffers.words."""
+    from . import _C
+    rank = dist.get_rank(group) if buffers.ranks > 1 else 0
+    _C.visibility_pack(visible_count, out=buffers.words[rank])
+    if buffers.ranks > 1:
+        dist.all_gather([buffers.words[r] for r in range(buffers.ranks)], buffers.words[rank].clone(), group=group)
+    return buffers.words.numel() * buffers.words.element_size()
+
+
+@torch.no_grad()
+def compact_allreduce(tensors, visible_count, group=None, compact_below=COMPACT_BELOW, bounds=None, buffers=None):
+    """SUM over the ranks of the (P, M) float32 tensors of `tensors` and of the (P,) `visible_count`,
+    exchanging only the rows some view of the step saw on some rank (a row no rank saw is zero on
+    every rank, and so is its sum):
+
+    1. pack `visible_count > 0` into bits (_C.visibility_pack);
+    2. all-gather the ranks' words ((P + 31) // 32 per rank; an all-gather works on every backend, and
+       RCCL's reductions have no bitwise OR);
+    3. OR them into the ascending list of the U union rows (_C.union_plan);
+    4. if U >= compact_below * P, stop here and return mode "dense": nothing has been reduced and
+       the caller all-reduces its buffers as it would without this function;
+    5. otherwise gather the union rows of every tensor and of the count into the compact buffer
+       ([group][union row][column], compact_layout), all-reduce its U * (sum(M) + 1) floats in place
+       with one collective, and scatter them back (_C.rows_gather / _C.rows_scatter).
+
+    Every rank sees the same gathered words, so every rank computes the same U and takes the same
+    branch: the decision depends on U, P and compact_below and on nothing else (compact_below must be
+    the same on every rank).  With two ranks the result equals the dense all-reduce bit for bit.
+
+    bounds: optional Gaussian boundaries (multiples of _C.union_rows_per_wave(), or P) whose ranks in
+    the row list are returned as "bound_ranks".  buffers: a CompactBuffers to reuse.  Returns
+    {"mode": "compact" | "dense", "U", "P", "bytes": what this call put on the wire per rank,
+    "bound_ranks", "buffers"}.  GPU tensors only; needs an initialised process group."""
+    from . import _C
+    P = visible_count.numel()
+    ranks = dist.get_world_size(group)
+    if buffers is None or buffers.P != P or buffers.ranks != ranks:
+        buffers = CompactBuffers(P, ranks, visible_count.device)
+    wire = _gather_words(buffers, visible_count, group)
+    U, _, _, branks = _C.union_plan(buffers.words, P, bounds=bounds, rows=buffers.rows, mask=buffers.mask,
+                                    workspace=buffers.workspace)
+    info = {"mode": "dense", "U": U, "P": P, "bytes": wire, "bound_ranks": branks, "buffers": buffers}
+    if U >= compact_below * P:
+        return info
+    groups = [t.reshape(P, t.numel() // P) for t in tensors] + [visible_count]
+    n = compact_layout(U, [g.numel() // P for g in groups])[-1]
+    info["mode"] = "compact"
+    if n:
+        compact = buffers.compact_for(n)[:n]
+        _C.rows_gather(groups, buffers.rows, U, compact)
+        dist.all_reduce(compact, op=dist.ReduceOp.SUM, group=group)
+        _C.rows_scatter(groups, buffers.rows, U, compact)
+        info["bytes"] += n * 4
+    return info
+
+
 def max_over_ranks(seconds, device=None, group=None):
     """The slowest rank's wall time (the bench's timed region)."""
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
@@ -381,13 +479,33 @@ class DataParallelTrainer:
     accumulate_grads_in_place(), so the backward kernel adds the three raw gradients straight into
     the flat buffer (the arithmetic of autograd's AccumulateGrad, without its three passes).  The
     values agree with the torch chain to fp32 rounding.
+
+    `compact_reduce=True` (opt-in, GPU parameters; off: nothing changes, not a launch, not a bit):
+    step 3 exchanges only the rows some view of the step saw on some rank (`compact_allreduce`: the
+    ranks all-gather one visibility bit per Gaussian, every rank derives the same ascending list of
+    the U union rows, and one all-reduce of U x 60 floats at SH degree 3 replaces the one of P x 60;
+    the exposure gradients get a small all-reduce of their own).  Rows outside the union are zero on
+    every rank already, so the flat buffer afterwards equals what the dense all-reduce leaves -- bit
+    for bit with two ranks.  When the union is `compact_below` x P rows or more (default
+    COMPACT_BELOW; the same on every rank) the step falls back to the dense collective on its own;
+    every rank takes the same branch because the decision depends on the gathered bits only.  The
+    pipelined step (`reduce_and_step`) plans once, rounds its Gaussian boundaries to
+    _C.union_rows_per_wave() and then, range by range, gathers that window of the union, all-reduces
+    it, scatters it back and steps the optimizer on the range.  `last_reduce` holds the last
+    exchange's {"mode", "U", "P", "bytes"}.
     """
 
     def __init__(self, raw, lr=None, optimizer="sparse_adam", lambda_dssim=0.2, bg=None, group=None, batched=True,
                  seed=0, exposures=None, spatial_lr_scale=None, opt=None, pipeline_chunks=4, fused_tail=False,
-                 fused_densify=False, fused_activations=False, fused_view_loss=False):
+                 fused_densify=False, fused_activations=False, fused_view_loss=False,
+                 compact_reduce=False, compact_below=None):
         import diff_gaussian_rasterization as dgr
         self._dgr = dgr
+        # step 3 over the union of the ranks' visible rows only (off: the dense all-reduce)
+        self.compact_reduce = compact_reduce
+        self.compact_below = COMPACT_BELOW if compact_below is None else float(compact_below)
+        self.last_reduce = None
+        self._compact = None
         # exp / sigmoid / normalize of the raw parameters as one dgr.fused_activations call (off: torch)
         self.fused_activations = fused_activations
         # densify_and_prune as the two HIP calls of fused_densify_and_prune (off: the torch chain)
@@ -470,6 +588,9 @@ class DataParallelTrainer:
                     self.optimizer.state[new] = st
         self.params = params
         self.stats = densification_stats(P, dev)
+        self._compact = None
+        if self.compact_reduce and dev.type == "cuda" and dist.is_initialized():
+            self._compact = CompactBuffers(P, dist.get_world_size(self.group), dev)
 
     def activations(self):
         """GaussianModel.get_* (gaussian_model.py:102-135): the torch chain, or with
@@ -637,8 +758,35 @@ class DataParallelTrainer:
         """Step 3: one in-place all_reduce(SUM) of gradients + visibility counts.  Returns bytes."""
         if not dist.is_initialized() or dist.get_world_size(self.group) == 1:
             return 0
+        if self.compact_reduce and self.P:
+            return self._compact_reduce()
         dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
         return self.flat.numel() * self.flat.element_size()
+
+    def _grad_rows(self):
+        """The six gradient tensors as (P, M) views of the flat buffer."""
+        return [self.params[k].grad.view(self.P, self.params[k].numel() // self.P) for k in TRAIN_GROUPS]
+
+    def _reduce_exposure_grads(self):
+        if self.exposures is None:
+            return 0
+        dist.all_reduce(self.exposures.grad, op=dist.ReduceOp.SUM, group=self.group)
+        return self.exposures.grad.numel() * 4
+
+    def _compact_reduce(self):
+        """reduce() with `compact_reduce`: one compact_allreduce over the gradients and the visibility
+        counts (or, where the union is too large, the dense collective), the exposure gradients apart."""
+        info = compact_allreduce(self._grad_rows(), self.visible_count, self.group, self.compact_below,
+                                 buffers=self._compact)
+        self._compact = info.pop("buffers")
+        info.pop("bound_ranks")
+        if info["mode"] == "dense":
+            dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group)
+            info["bytes"] += self.flat.numel() * self.flat.element_size()
+        else:
+            info["bytes"] += self._reduce_exposure_grads()
+        self.last_reduce = info
+        return info["bytes"]
 
     @torch.no_grad()
     def optimizer_step(self):
@@ -692,6 +840,8 @@ class DataParallelTrainer:
         densifies between the reduction and the step.)"""
         P = self.P
         chunks = max(1, min(chunks or self.pipeline_chunks, P))
+        if self.compact_reduce and P and self._compact_reduce_and_step(chunks):
+            return
         bounds = [(P * k // chunks, P * (k + 1) // chunks) for k in range(chunks)]
         works = []
         for g0, g1 in bounds:
@@ -709,6 +859,50 @@ class DataParallelTrainer:
                 x.wait()
             visible[g0:g1] = self.visible_count[g0:g1] > 0
             self.optimizer.step(visible, P, rows=(g0, g1))
+
+    def _compact_reduce_and_step(self, chunks):
+        """reduce_and_step over the union rows: pack, all-gather and plan once; then per Gaussian range
+        (boundaries rounded to _C.union_rows_per_wave()) gather the range's window of the union, reduce
+        the window's slice of every group asynchronously, wait, scatter it back and step the optimizer
+        on the range.  Returns False, having reduced nothing, when the union is compact_below x P rows or
+        more: the caller then runs the dense pipeline."""
+        from . import _C
+        P = self.P
+        if self._compact is None:
+            self._compact = CompactBuffers(P, dist.get_world_size(self.group), self.device)
+        buf = self._compact
+        rpw = _C.union_rows_per_wave()
+        cuts = [0] + [min(P, (P * k // chunks + rpw // 2) // rpw * rpw) for k in range(1, chunks)] + [P]
+        cuts = sorted(set(cuts))
+        wire = _gather_words(buf, self.visible_count, self.group)
+        U, _, _, ranks = _C.union_plan(buf.words, P, bounds=cuts, rows=buf.rows, mask=buf.mask,
+                                       workspace=buf.workspace)
+        info = {"mode": "dense", "U": U, "P": P, "bytes": wire}
+        self.last_reduce = info
+        if U >= self.compact_below * P:
+            info["bytes"] += self.flat.numel() * 4  # (the dense pipeline reduces every element once)
+            return False
+        info["mode"] = "compact"
+        groups = self._grad_rows() + [self.visible_count]
+        Ms = [g.numel() // P for g in groups]
+        off = compact_layout(U, Ms)
+        compact = buf.compact_for(off[-1])
+        works = []
+        for u0, u1 in zip(ranks[:-1], ranks[1:]):
+            _C.rows_gather(groups, buf.rows, U, compact, window=(u0, u1))
+            works.append([dist.all_reduce(compact[o + u0 * M:o + u1 * M], op=dist.ReduceOp.SUM, group=self.group,
+                                          async_op=True) for o, M in zip(off, Ms) if M and u1 > u0])
+        info["bytes"] += off[-1] * 4
+        if self.exposures is not None:
+            info["bytes"] += self._reduce_exposure_grads()
+            self.exposure_optimizer.step()
+        for (g0, g1), (u0, u1), w in zip(zip(cuts[:-1], cuts[1:]), zip(ranks[:-1], ranks[1:]), works):
+            for x in w:
+                x.wait()
+            _C.rows_scatter(groups, buf.rows, U, compact, window=(u0, u1))
+            # buf.mask is the union: visible_count > 0 after the reduction, row for row
+            self.optimizer.step(buf.mask, P, rows=(g0, g1))
+        return True
 
     def step(self, views, depth_weight=0.0):
         self.zero_grad()

@@ -465,6 +465,56 @@ int gsr_densify_apply(int P, int P_after, int n_split, int N, int n_groups, cons
                       float* const* dst_m, float* const* dst_v, const float* samples, const char* workspace,
                       gsr_stream_t stream);
 
+/* Visibility-compacted gradient exchange for data-parallel steps.  A Gaussian no view of a step saw on
+ * any rank has a zero gradient row on every rank, so the SUM over the ranks needs only the union of the
+ * ranks' visible rows.  Each rank packs its visibility counts into bits (gsr_visibility_pack), the
+ * ranks exchange the words, gsr_union_plan ORs them into the ascending list of union rows, and
+ * gsr_rows_gather / gsr_rows_scatter move those rows of every gradient tensor into and out of a
+ * compact buffer that the collective then reduces.  Every rank that plans the same words gets the
+ * same U and the same list.
+ *
+ * Bit layout: Gaussian g is bit (g & 31) of word (g >> 5); a row of words has (P + 31) / 32 words;
+ * bits at or beyond P are zero.
+ * Compact layout: [group][union row][column] -- group k starts at U * (Ms[0] + .. + Ms[k-1]) floats,
+ * union row u of it at another u * Ms[k]; U * sum(Ms) floats in all.
+ * All device arrays are contiguous and need 4-byte alignment only, except the workspace (256).
+ *
+ * gsr_union_rows_per_wave: the Gaussians one wave of the plan covers; boundaries are multiples of it.
+ * gsr_union_workspace_size: bytes of device memory gsr_union_plan needs for P Gaussians (0 for P <= 0). */
+int gsr_union_rows_per_wave(void);
+size_t gsr_union_workspace_size(int P);
+
+/* words[w] bit b = (count[32 w + b] > 0) for the P floats of `count` (device); every one of the
+ * (P + 31) / 32 words (device) is written in full.  P == 0: nothing is launched.  Asynchronous. */
+int gsr_visibility_pack(int P, const float* count, uint32_t* words, gsr_stream_t stream);
+
+/* The plan.  words: (ranks, (P + 31) / 32) device words, one row per rank (ranks >= 1); tail bits at
+ * or beyond P are ignored.  workspace: gsr_union_workspace_size(P) bytes of device memory, 256-byte
+ * aligned.  rows: P device words; rows[0 .. U) become the union's Gaussians in ascending order, the
+ * rest is not written.  mask: P device bytes (1 = in the union), or NULL.  bounds: n_bounds <= 16 HOST
+ * ints, each P or a multiple of gsr_union_rows_per_wave() in [0, P].  U and bound_ranks (n_bounds HOST
+ * ints: the number of union rows below each boundary, i.e. the boundary's index into rows) are
+ * written before the call returns.  Synchronises `stream` once.  P == 0: U and the ranks are zero,
+ * nothing is launched.  ranks < 1, more than 16 boundaries or an unaligned boundary:
+ * GSR_ERR_INVALID. */
+int gsr_union_plan(int P, int ranks, const uint32_t* words, int n_bounds, const int* bounds, char* workspace,
+                   uint32_t* rows, uint8_t* mask, int* U, int* bound_ranks, gsr_stream_t stream);
+
+/* compact[group k][u][c] = src[k][rows[u] * Ms[k] + c] for the window u0 <= u < u1 of the U union rows,
+ * every group in one launch.  n_groups <= 8; src: HOST array of device pointers to the (P, Ms[k])
+ * tensors; a group with Ms[k] == 0 is skipped (its pointer may be NULL).  rows: gsr_union_plan's list;
+ * an entry >= P is skipped.  compact: U * sum(Ms) device floats; only the window's elements are
+ * written.  U * Ms[k] < 2^32 - 16.  P == 0, U == 0 or an empty window: nothing is launched.  A window
+ * outside [0, U], U > P or more than 8 groups: GSR_ERR_INVALID.  Asynchronous. */
+int gsr_rows_gather(int P, int U, int u0, int u1, int n_groups, const int* Ms, const float* const* src,
+                    const uint32_t* rows, float* compact, gsr_stream_t stream);
+
+/* The inverse: dst[k][rows[u] * Ms[k] + c] = compact[group k][u][c] for u0 <= u < u1.  Only the union
+ * rows of the window are written; no other row of dst is touched.  Arguments and refusals as
+ * gsr_rows_gather.  Asynchronous. */
+int gsr_rows_scatter(int P, int U, int u0, int u1, int n_groups, const int* Ms, float* const* dst,
+                     const uint32_t* rows, const float* compact, gsr_stream_t stream);
+
 /* Where the forward's binning prefix (preprocess .. tile order) runs.  on = 1: on an internal
  * stream of the highest priority, forked from and joined back into the caller's stream, its side
  * work (record-slot scan, tile histogram, forward tile order) on a second internal stream;

@@ -39,7 +39,11 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          "densify_decide_kernel": "densify_plan", "densify_offsets_kernel": "densify_plan",
          "densify_scatter_kernel": "densify_plan", "densify_apply_kernel": "densify_apply",
          # the parameter activations (diff_gaussian_rasterization.fused_activations)
-         "activate_fwd_kernel": "activate_fwd", "activate_bwd_kernel": "activate_bwd"}
+         "activate_fwd_kernel": "activate_fwd", "activate_bwd_kernel": "activate_bwd",
+         # the visibility-compacted gradient exchange (multiview.compact_allreduce)
+         "visibility_pack_kernel": "visibility_pack", "union_count_kernel": "union_plan",
+         "union_offsets_kernel": "union_plan", "union_rows_kernel": "union_plan",
+         "rows_move_kernel": "rows_gather_scatter"}
 # the kernel bench.py --pmc-child launches between its warm-up and its counted steps
 MARKER = "spin_kernel"
 # operations made of several kernels (several dispatches per call)

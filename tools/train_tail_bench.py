@@ -35,6 +35,17 @@
           the optimizer step the same.  Wall clock: time.perf_counter() around synchronised groups of
           --group iterations, the two sides alternating group by group -- the host's dispatch cost is
           part of what is compared.  A report, not a gate.
+  compact: the device side of multiview.compact_allreduce on ONE GPU, without a collective: for a
+          (P, 60) gradient buffer at SH degree 3 (six gradient groups and the count column) and union
+          masks at 0.25 / 0.5 / 0.75 / 1.0 of P (random) and the bench scene's own 8-view union,
+          _C.visibility_pack + _C.union_plan (with its stream synchronisation), _C.rows_gather and
+          _C.rows_scatter, beside a plain clone() of the same buffer as the HBM yardstick -- the four
+          alternate call by call.  Byte models: pack + plan 4 B in per Gaussian, three passes over the
+          P / 8 B of bits, 1 B of mask out and 4 B per union row; gather and scatter 4 + 8 x 60 = 484 B
+          per union row each; clone 2 x 240 B per Gaussian.  The block also records the union fraction
+          U / P of the scenes the repository has (the trainer test's spread scene, the chair fixture,
+          the config-3-scale cloud) and the compact_below the measured copies give with DESIGN.md §8's
+          ASSUMED link rate.  Nothing here is timed on more than one GPU.
 
 Defaults are the bench's flagship shape: 8 views, 1920x1080, 1M Gaussians, seed-0 data.  The two
 sides alternate call by call; every call is bracketed by device events and ends in a
@@ -55,7 +66,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-npu_amd"))
 
 
-LEGS = ("loss", "view_loss", "stats", "densify", "activations", "iteration")
+LEGS = ("loss", "view_loss", "stats", "densify", "activations", "iteration", "compact")
 
 
 def timed(fn, torch):
@@ -144,6 +155,8 @@ def main():
         result["activations"] = activations_leg(args, side, torch, dev)
     if "iteration" in legs:
         result["iteration"] = iteration_leg(args, side, torch, fused_l1_ssim_loss, fused_ssim, dev)
+    if "compact" in legs:
+        result["compact"] = compact_leg(args, torch, multiview, dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
@@ -539,6 +552,143 @@ def iteration_leg(args, side, torch, fused_l1_ssim_loss, fused_ssim, dev):
                      "fused_l1_ssim_loss (V = 1); both: GaussianRasterizer with dc=, SparseGaussianAdam.step")
     out["agreement"] = {"first_iteration_loss_torch": first["torch"], "first_iteration_loss_fused": first["fused"],
                         "first_iteration_loss_abs_diff": abs(first["torch"] - first["fused"])}
+    return out
+
+
+def _radii_union(torch, dgr, scene, cams, W, H, dev, subsets):
+    """U / P of the union of the views' radii > 0 for each subset of `cams` (objects with the
+    synthetic.Camera fields), from real forward passes."""
+    sc = {k: v.to(dev) for k, v in scene.items()}
+    P = sc["means3D"].shape[0]
+    seen = []
+    with torch.no_grad():
+        for c in cams:
+            s = dgr.GaussianRasterizationSettings(
+                image_height=H, image_width=W, tanfovx=c.tanfovx, tanfovy=c.tanfovy, bg=torch.zeros(3, device=dev),
+                scale_modifier=1.0, viewmatrix=c.world_view_transform.to(dev),
+                projmatrix=c.full_proj_transform.to(dev), sh_degree=3, campos=c.camera_center.to(dev),
+                prefiltered=False, debug=False, antialiasing=False)
+            radii = dgr.GaussianRasterizer(raster_settings=s)(
+                means3D=sc["means3D"], means2D=torch.zeros_like(sc["means3D"]), shs=sc["shs"],
+                opacities=sc["opacities"], scales=sc["scales"], rotations=sc["rotations"])[1]
+            seen.append(radii > 0)
+    out = {"points": P, "resolution": [W, H], "per_view": [float(m.sum()) / P for m in seen]}
+    for name, idx in subsets.items():
+        out[name] = float(torch.stack([seen[i] for i in idx]).any(dim=0).sum()) / P
+    return out, torch.stack(seen).any(dim=0)
+
+
+def compact_leg(args, torch, multiview, dev):
+    """pack + plan, gather and scatter against a clone of the buffer, and the union fractions of the
+    repository's scenes (see the module docstring).  One GPU, no collective."""
+    import numpy as np
+
+    import diff_gaussian_rasterization as dgr
+    from diff_gaussian_rasterization import _C
+    for p in (ROOT, os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import nerf_synthetic as ns
+    import synthetic
+    P, H, W = args.points, args.height, args.width
+    Ms = (3, 3, 45, 1, 3, 4, 1)
+    M = sum(Ms)
+
+    # union fractions of the scenes at hand
+    class Cam:
+        def __init__(self, f, i):
+            self.world_view_transform = torch.from_numpy(f["train_viewmatrix"][i].copy())
+            self.full_proj_transform = torch.from_numpy(f["train_projmatrix"][i].copy())
+            self.camera_center = torch.from_numpy(f["train_campos"][i].copy())
+            self.tanfovx, self.tanfovy = float(f["train_tanfov"][i][0]), float(f["train_tanfov"][i][1])
+    ring8 = {"views_0_3": [0, 1, 2, 3], "views_4_7": [4, 5, 6, 7], "all_8_views": list(range(8))}
+    unions = {}
+    spread = synthetic.make_scene(2000, seed=0)
+    spread["means3D"] = spread["means3D"] * 3.0
+    unions["trainer_test_scene_spread_3"], _ = _radii_union(
+        torch, dgr, spread, [synthetic.Camera(128, 96, view=v) for v in range(8)], 128, 96, dev, ring8)
+    unions["trainer_test_scene_spread_1"], _ = _radii_union(
+        torch, dgr, synthetic.make_scene(2000, seed=0), [synthetic.Camera(128, 96, view=v) for v in range(8)], 128,
+        96, dev, ring8)
+    golden = os.path.join(ROOT, "tests", "golden", "chair")
+    f, fr = dict(np.load(os.path.join(golden, "nerf_chair.npz"))), dict(np.load(os.path.join(golden, "chair_frames.npz")))
+    chair = ns.initial_gaussians(f["xyz"], f["rgb"], f["dist2"], scale=f["scale"], opacity=f["opacity"])
+    unions["chair_fixture_train_cameras"], _ = _radii_union(
+        torch, dgr, chair, [Cam(fr, i) for i in range(8)], 800, 800, dev,
+        {"views_0_3": [0, 1, 2, 3], "all_8_views": list(range(8))})
+    unions["config3_scale_cloud"], _ = _radii_union(
+        torch, dgr, synthetic.make_scene(6_000_000, seed=0), [synthetic.Camera(1297, 840, view=v) for v in range(8)],
+        1297, 840, dev, {"views_0_3": [0, 1, 2, 3], "all_8_views": list(range(8))})
+    torch.cuda.empty_cache()
+    bench_union, bench_mask = _radii_union(
+        torch, dgr, synthetic.make_scene(P, seed=0), [synthetic.Camera(W, H, view=v) for v in range(8)], W, H, dev,
+        {"all_8_views": list(range(8))})
+    unions["bench_scene"] = bench_union
+    torch.cuda.empty_cache()
+
+    g = torch.Generator(device="cpu").manual_seed(0)
+    flat = torch.randn((P * M,), generator=g).to(dev)
+    groups, off = [], 0
+    for m in Ms:
+        groups.append(flat[off:off + P * m].view(P, m))
+        off += P * m
+    masks = {f"random_{q}": (torch.rand((P,), generator=g) < q).to(dev) for q in (0.25, 0.5, 0.75)}
+    masks["random_1.0"] = torch.ones((P,), dtype=torch.bool, device=dev)
+    masks["bench_scene_8_views"] = bench_mask
+    words = torch.empty((1, _C.visibility_words(P)), dtype=torch.int32, device=dev)
+    rows = torch.empty((P,), dtype=torch.int32, device=dev)
+    mask_out = torch.empty((P,), dtype=torch.bool, device=dev)
+    ws = torch.empty((int(_C.lib.gsr_union_workspace_size(P)),), dtype=torch.uint8, device=dev)
+    compact = torch.empty((P * M,), device=dev)
+    out = {"groups": list(Ms), "floats_per_row": M, "points": P,
+           "note": "one GPU, no collective: nothing here was timed on more than one GPU", "masks": {}}
+    held = {}
+    for name, mask in masks.items():
+        count = mask.to(torch.float32)
+
+        def pack_plan():
+            _C.visibility_pack(count, out=words[0])
+            held["U"] = _C.union_plan(words, P, rows=rows, mask=mask_out, workspace=ws)[0]
+        pack_plan()
+        U = held["U"]
+        assert U == int(mask.sum()) and torch.equal(mask_out, mask)
+        sides = {"clone": lambda: held.__setitem__("c", flat.clone()), "pack_plan": pack_plan,
+                 "gather": lambda: _C.rows_gather(groups, rows, U, compact),
+                 "scatter": lambda: _C.rows_scatter(groups, rows, U, compact)}
+        # gather then scatter puts back what it took: the buffer stays as it was
+        sides["gather"]()
+        before = flat.clone()
+        sides["scatter"]()
+        assert torch.equal(before.view(torch.int32), flat.view(torch.int32))
+        del before
+        r = alternate(sides, args.warmup, args.reps, args.rounds, torch)
+        nbytes = {"clone": 2 * 4 * M * P, "pack_plan": 4 * P + 3 * (P // 8) + P + 4 * U,
+                  "gather": (4 + 8 * M) * U, "scatter": (4 + 8 * M) * U}
+        block = {"U": U, "union_fraction": U / P}
+        for k, (med, spread_ms, rounds) in r.items():
+            block[k] = {"median_ms": med, "spread_ms": spread_ms, "round_medians_ms": rounds,
+                        "algorithmic_bytes": nbytes[k], "algorithmic_GBps": nbytes[k] / (med * 1e-3) / 1e9}
+        out["masks"][name] = block
+    # compact_below from the measured copies (random_0.5) and DESIGN.md §8's ASSUMED link rate
+    half = out["masks"]["random_0.5"]
+    per_row_s = (half["gather"]["median_ms"] + half["scatter"]["median_ms"]) * 1e-3 / half["U"]
+    fixed_s = half["pack_plan"]["median_ms"] * 1e-3
+    bus = {2: 55.0, 4: 150.0, 8: 330.0}  # DESIGN.md §8's ASSUMED RCCL bus rates over xGMI, GB/s
+    derived = {"assumed_bus_GBps": {str(k): v for k, v in bus.items()}, "dense_bytes_per_row": 4 * M,
+               "measured_gather_plus_scatter_s_per_union_row": per_row_s,
+               "measured_pack_plan_s": fixed_s, "by_world_size": {}}
+    for N in (2, 4, 8):
+        link_s = 2.0 * (N - 1) / N * 4 * M / (bus[N] * 1e9)  # link time of one row of the dense all-reduce
+        # compaction pays while  f * per_row_s + fixed_s / P  <  (1 - f) * link_s
+        f = (link_s - fixed_s / P) / (link_s + per_row_s)
+        derived["by_world_size"][str(N)] = {"link_s_per_row": link_s, "break_even_fraction": f,
+                                            "rounded_down_to_0.05": int(f / 0.05 + 1e-9) * 0.05}
+    derived["note"] = ("break-even union fraction: gather + scatter time per union row (measured, one GPU) against the "
+                       "link time saved per row left out (ring factor 2(N-1)/N, bus rates ASSUMED, not measured); "
+                       "the shipped default follows N = 8")
+    out["compact_below_derivation"] = derived
+    out["shipped_compact_below"] = multiview.COMPACT_BELOW
+    out["union_fractions"] = unions
     return out
 
 
