@@ -52,17 +52,160 @@ struct SsGrid {
 };
 
 struct SsTile {
-    size_t plane;  // offset of the tile's plane
+    size_t plane;  // offset of the tile's plane, z H W
     int x0, y0;
+    int z;         // index of the tile's plane
 };
 
+// The one decoding of a tile index: tiles run along x, then y, then over the planes.
 __device__ __forceinline__ SsTile ss_tile(const SsGrid& g, int t)
 {
     const int x = t % g.tx, r = t / g.tx, y = r % g.ty, z = r / g.ty;
-    return {(size_t)z * g.H * g.W, x * SS_TW, y * SS_TH};
+    return {(size_t)z * g.H * g.W, x * SS_TW, y * SS_TH, z};
 }
 
 __device__ __forceinline__ f2 pk_fma(float w, f2 a, f2 c) { return __builtin_elementwise_fma(f2{w, w}, a, c); }
+
+// ---- the 11x11 window, shared by every kernel below ------------------------------------------------
+// Halo registers -> LDS: put(i, j) stores this thread's element j at index i of the staged planes.
+template <class Put>
+__device__ __forceinline__ void ss_stage(Put put)
+{
+#pragma unroll
+    for (int j = 0; j < SS_STAGE_IT; j++) {
+        const int i = threadIdx.x + j * 256;
+        if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+        put(i, j);
+    }
+}
+
+// Horizontal pass over the five moments x, y, xx, yy, xy of the staged planes s1 (x) and s2 (y).
+__device__ __forceinline__ void ss_hpass_moments(const SsimWeights& wt, const float (&s1)[SS_STAGE],
+                                                 const float (&s2)[SS_STAGE], f2 (&hs)[5][SS_HH][32], int p, int q)
+{
+    for (int r = q; r < SS_HH; r += 8) {
+        f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
+        const float* r1 = s1 + r * SS_LS + p;
+        const float* r2 = s2 + r * SS_LS + p;
+#pragma unroll
+        for (int k = 0; k < 11; k++) {
+            const f2 a = {r1[k], r1[k + 32]}, b = {r2[k], r2[k + 32]};
+            const float w = wt.w[k];
+            mx = pk_fma(w, a, mx);
+            my = pk_fma(w, b, my);
+            mxx = pk_fma(w, a * a, mxx);
+            myy = pk_fma(w, b * b, myy);
+            mxy = pk_fma(w, a * b, mxy);
+        }
+        hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
+    }
+}
+
+// Horizontal pass over three staged planes.
+__device__ __forceinline__ void ss_hpass_planes(const SsimWeights& wt, const float (&gs)[3][SS_STAGE],
+                                                f2 (&hs)[3][SS_HH][32], int p, int q)
+{
+    for (int r = q; r < SS_HH; r += 8) {
+        f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+        for (int k = 0; k < 11; k++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float* row = gs[c] + r * SS_LS + p;
+                s[c] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[c]);
+            }
+        }
+        hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
+    }
+}
+
+// Vertical pass over N planes: each of the 14 halo rows thread row q needs is read once and folded
+// into all four of its outputs, out[i] = rows 4q + i of the column pair.
+template <int N>
+__device__ __forceinline__ void ss_vpass(const SsimWeights& wt, const f2 (&hs)[N][SS_HH][32], int p, int q,
+                                         f2 (&out)[4][N])
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int k = 0; k < N; k++) out[i][k] = f2{0.f, 0.f};
+#pragma unroll
+    for (int rr = 0; rr < 14; rr++) {
+        f2 v[N];
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] = hs[k][4 * q + rr][p];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int tap = rr - i;
+            if (tap < 0 || tap > 10) continue;
+#pragma unroll
+            for (int k = 0; k < N; k++) out[i][k] = pk_fma(wt.w[tap], v[k], out[i][k]);
+        }
+    }
+}
+
+// SSIM of one pixel (column h of the pair) from its five windowed moments; with `partials` also
+// d[0..2] = dmap/dmu_x (through sigma_xx and sigma_xy included), dmap/dsigma_xx, dmap/dsigma_xy.
+__device__ __forceinline__ float ss_pixel(const f2 (&m)[5], int h, float C1, float C2, bool partials, float (&d)[3])
+{
+    const float mu1 = m[0][h], mu2 = m[1][h];
+    const float s11 = m[2][h] - mu1 * mu1, s22 = m[3][h] - mu2 * mu2;
+    const float s12 = m[4][h] - mu1 * mu2;
+    const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
+    const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
+    const float inv = 1.f / (Cc * D);
+    const float val = A * B * inv;
+    if (partials) {
+        // d map / d mu1 = 2 mu2 B / (C D) - 2 mu1 val / C, with 1/C = D inv, 1/D = C inv
+        const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
+        const float f_s11 = -val * Cc * inv;
+        const float f_s12 = 2.f * A * inv;
+        d[0] = f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12;
+        d[1] = f_s11;
+        d[2] = f_s12;
+    }
+    return val;
+}
+
+// dL/dx of one pixel from the three windowed sums: (w * gA) + 2 x (w * gB) + y (w * gC).
+__device__ __forceinline__ float ss_bwd_pixel(const f2 (&s)[3], int h, float x, float y)
+{
+    return s[0][h] + 2.f * x * s[1][h] + y * s[2][h];
+}
+
+// This thread's output pixels of the tile at (x0, y0) that lie inside the image: f(i, h, y, x) for row i
+// of its four and column h of its pair.
+template <class F>
+__device__ __forceinline__ void ss_pixels(const SsGrid& g, int x0, int y0, int p, int q, F f)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int y = y0 + 4 * q + i;
+        if (y >= g.H) break;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int x = x0 + p + 32 * h;
+            if (x >= g.W) continue;
+            f(i, h, y, x);
+        }
+    }
+}
+
+// ... and their values in two planes, read ahead of the window (a pixel outside reads element 0, unused).
+__device__ __forceinline__ void ss_load_pixels(const float* a, const float* b, const SsGrid& g, int x0, int y0, int p,
+                                               int q, float (&va)[4][2], float (&vb)[4][2])
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int y = y0 + 4 * q + j, x = x0 + p + 32 * h;
+            const size_t o = (y < g.H && x < g.W) ? (size_t)y * g.W + x : 0;
+            va[j][h] = a[o];
+            vb[j][h] = b[o];
+        }
+    }
+}
 
 // This thread's NP-plane share of one tile's halo, held in registers between the load (issued one
 // tile ahead) and the LDS store.  Elements outside the image / the 74 columns load from the plane
@@ -106,80 +249,27 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(SsGrid g, float C1, float
     for (; t < g.ntiles; t += gridDim.x) {
         const SsTile cur = ss_tile(g, t);
         __syncthreads();  // the previous tile is done with s1, s2 and hs
-#pragma unroll
-        for (int j = 0; j < SS_STAGE_IT; j++) {
-            const int i = threadIdx.x + j * 256;
-            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+        ss_stage([&](int i, int j) {
             s1[i] = halo.get(0, j);
             s2[i] = halo.get(1, j);
-        }
+        });
         if (t + (int)gridDim.x < g.ntiles) halo.load(src, g, ss_tile(g, t + gridDim.x));
         __syncthreads();
-        for (int r = q; r < SS_HH; r += 8) {
-            f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
-            const float* r1 = s1 + r * SS_LS + p;
-            const float* r2 = s2 + r * SS_LS + p;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const f2 a = {r1[k], r1[k + 32]}, b = {r2[k], r2[k + 32]};
-                const float w = wt.w[k];
-                mx = pk_fma(w, a, mx);
-                my = pk_fma(w, b, my);
-                mxx = pk_fma(w, a * a, mxx);
-                myy = pk_fma(w, b * b, myy);
-                mxy = pk_fma(w, a * b, mxy);
-            }
-            hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
-        }
+        ss_hpass_moments(wt, s1, s2, hs, p, q);
         __syncthreads();
-        // vertical pass: each of the 14 halo rows thread row q needs is read once and folded
-        // into all four of its outputs
         f2 m4[4][5];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) m4[i][k] = f2{0.f, 0.f};
-#pragma unroll
-        for (int rr = 0; rr < 14; rr++) {
-            f2 v[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) v[k] = hs[k][4 * q + rr][p];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int tap = rr - i;
-                if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                for (int k = 0; k < 5; k++) m4[i][k] = pk_fma(wt.w[tap], v[k], m4[i][k]);
+        ss_vpass(wt, hs, p, q, m4);
+        ss_pixels(g, cur.x0, cur.y0, p, q, [&](int i, int h, int y, int x) {
+            float d[3];
+            const float val = ss_pixel(m4[i], h, C1, C2, TRAIN, d);
+            const size_t o = cur.plane + (size_t)y * g.W + x;
+            map[o] = val;
+            if constexpr (TRAIN) {
+                dA[o] = d[0];
+                dB[o] = d[1];
+                dC[o] = d[2];
             }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int y = cur.y0 + 4 * q + i;
-            if (y >= g.H) break;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int x = cur.x0 + p + 32 * h;
-                if (x >= g.W) continue;
-                const float mu1 = m4[i][0][h], mu2 = m4[i][1][h];
-                const float s11 = m4[i][2][h] - mu1 * mu1, s22 = m4[i][3][h] - mu2 * mu2;
-                const float s12 = m4[i][4][h] - mu1 * mu2;
-                const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
-                const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
-                const float inv = 1.f / (Cc * D);
-                const float val = A * B * inv;
-                const size_t o = cur.plane + (size_t)y * g.W + x;
-                map[o] = val;
-                if constexpr (TRAIN) {
-                    // d map / d mu1 = 2 mu2 B / (C D) - 2 mu1 val / C, with 1/C = D inv, 1/D = C inv
-                    const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
-                    const float f_s11 = -val * Cc * inv;
-                    const float f_s12 = 2.f * A * inv;
-                    dA[o] = f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12;
-                    dB[o] = f_s11;
-                    dC[o] = f_s12;
-                }
-            }
-        }
+        });
     }
 }
 
@@ -198,73 +288,24 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(SsGrid g, SsimWeights wt,
     halo.load(src, g, ss_tile(g, t));
     for (; t < g.ntiles; t += gridDim.x) {
         const SsTile cur = ss_tile(g, t);
-        // this thread's output pixels' img1 / img2 values
-        float i1[4][2], i2[4][2];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int y = cur.y0 + 4 * q + j, x = cur.x0 + p + 32 * h;
-                const size_t o = cur.plane + ((y < g.H && x < g.W) ? (size_t)y * g.W + x : 0);
-                i1[j][h] = img1[o];
-                i2[j][h] = img2[o];
-            }
-        }
+        float i1[4][2], i2[4][2];  // this thread's output pixels' img1 / img2 values
+        ss_load_pixels(img1 + cur.plane, img2 + cur.plane, g, cur.x0, cur.y0, p, q, i1, i2);
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SS_STAGE_IT; j++) {
-            const int i = threadIdx.x + j * 256;
-            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+        ss_stage([&](int i, int j) {
             const float gm = halo.get(0, j);
             gs[0][i] = gm * halo.v[1][j];
             gs[1][i] = gm * halo.v[2][j];
             gs[2][i] = gm * halo.v[3][j];
-        }
+        });
         if (t + (int)gridDim.x < g.ntiles) halo.load(src, g, ss_tile(g, t + gridDim.x));
         __syncthreads();
-        for (int r = q; r < SS_HH; r += 8) {
-            f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float* row = gs[c] + r * SS_LS + p;
-                    s[c] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[c]);
-                }
-            }
-            hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
-        }
+        ss_hpass_planes(wt, gs, hs, p, q);
         __syncthreads();
         f2 s4[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) s4[i][c] = f2{0.f, 0.f};
-#pragma unroll
-        for (int rr = 0; rr < 14; rr++) {
-            f2 v[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) v[c] = hs[c][4 * q + rr][p];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int tap = rr - i;
-                if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                for (int c = 0; c < 3; c++) s4[i][c] = pk_fma(wt.w[tap], v[c], s4[i][c]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int y = cur.y0 + 4 * q + j;
-            if (y >= g.H) break;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int x = cur.x0 + p + 32 * h;
-                if (x >= g.W) continue;
-                const size_t o = cur.plane + (size_t)y * g.W + x;
-                dimg1[o] = s4[j][0][h] + 2.f * i1[j][h] * s4[j][1][h] + i2[j][h] * s4[j][2][h];
-            }
-        }
+        ss_vpass(wt, hs, p, q, s4);
+        ss_pixels(g, cur.x0, cur.y0, p, q, [&](int j, int h, int y, int x) {
+            dimg1[cur.plane + (size_t)y * g.W + x] = ss_bwd_pixel(s4[j], h, i1[j][h], i2[j][h]);
+        });
     }
 }
 
@@ -291,12 +332,27 @@ struct PhotoTile {
 __device__ __forceinline__ PhotoTile photo_tile(const SsGrid& g, const PhotoViews& pv, const float* img, int t)
 {
     const SsTile a = ss_tile(g, t);
-    const int z = t / (g.tx * g.ty);
-    const int v = z / pv.C, c = z - v * pv.C;
-    return {a, {0, a.x0, a.y0}, img + a.plane, pv.gt[v] + (size_t)c * g.H * g.W, v};
+    const int v = a.z / pv.C, c = a.z - v * pv.C;
+    return {a, {0, a.x0, a.y0, a.z}, img + a.plane, pv.gt[v] + (size_t)c * g.H * g.W, v};
 }
 
 __device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }
+
+// x as the loss sees it, and whether torch's clamp backward passes its gradient
+__device__ __forceinline__ float clamped(int clamp, float x) { return clamp ? clamp01(x) : x; }
+__device__ __forceinline__ bool clamp_passes(int clamp, float x) { return !clamp || (x >= 0.f && x <= 1.f); }
+
+// The photometric term's gradient at a pixel the clamp passes, from the three windowed sums s:
+// dloss[v] (k_ssim (w * A + 2 x w * B + gt w * C) + k_l1 sign(x - gt)).  The callers select 0 where the
+// clamp is active (a select, not a product: the view loss's mask factor must not see a 0 to multiply).
+__device__ __forceinline__ float photo_bwd_pixel(const f2 (&s)[3], int h, float xv, float gt, float gv, float k_ssim,
+                                                 float k_l1)
+{
+    const float d = xv - gt;
+    const float sgn = (float)((d > 0.f) - (d < 0.f));
+    const float ssim = ss_bwd_pixel(s, h, xv, gt);
+    return gv * (k_ssim * ssim + k_l1 * sgn);
+}
 
 // lane 0 of each wave: the sum over its 64 lanes, in a fixed order
 __device__ __forceinline__ double wave_sum(double x)
@@ -306,8 +362,25 @@ __device__ __forceinline__ double wave_sum(double x)
     return x;
 }
 
+// The fixed-order sum over the workgroup's 256 threads, slot by slot of red: red_put (every thread),
+// a barrier, then red_total.  The callers place the barriers, also the one that keeps a new put from
+// overtaking the reads of the previous round.
+template <int K>
+__device__ __forceinline__ void red_put(double (&red)[4][K], int slot, double x)
+{
+    x = wave_sum(x);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][slot] = x;
+}
+
+template <int K>
+__device__ __forceinline__ double red_total(const double (&red)[4][K], int slot)
+{
+    return ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
+}
+
 // dA null: the loss alone (no backward will follow).  Two waves per SIMD (= SS_BLOCKS_PER_CU
-// workgroups per CU): without the bound the allocator takes 263 registers and one workgroup fits.
+// workgroups per CU), as a bound: the unbounded allocator has taken 263 registers for this kernel, so that
+// one workgroup fitted (246 as the code stands; the bound is what keeps a later change from costing a wave).
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 photo_loss_fwd_kernel(SsGrid g, PhotoViews pv, float C1, float C2, SsimWeights wt, int clamp, const float* img,
                       float* dA, float* dB, float* dC, double2* partial)
@@ -327,95 +400,39 @@ photo_loss_fwd_kernel(SsGrid g, PhotoViews pv, float C1, float C2, SsimWeights w
     for (; t < g.ntiles; t += gridDim.x) {
         const PhotoTile cur = photo_tile(g, pv, img, t);
         __syncthreads();  // the previous tile is done with s1, s2, hs and red
-#pragma unroll
-        for (int j = 0; j < SS_STAGE_IT; j++) {
-            const int i = threadIdx.x + j * 256;
-            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
-            const float a = halo.get(0, j);
-            s1[i] = clamp ? clamp01(a) : a;
+        ss_stage([&](int i, int j) {
+            s1[i] = clamped(clamp, halo.get(0, j));
             s2[i] = halo.get(1, j);
-        }
+        });
         if (t + (int)gridDim.x < g.ntiles) {
             const PhotoTile n = photo_tile(g, pv, img, t + gridDim.x);
             const float* const src[2] = {n.img, n.gt};
             halo.load(src, g, n.local);
         }
         __syncthreads();
-        for (int r = q; r < SS_HH; r += 8) {
-            f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
-            const float* r1 = s1 + r * SS_LS + p;
-            const float* r2 = s2 + r * SS_LS + p;
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-                const f2 a = {r1[k], r1[k + 32]}, b = {r2[k], r2[k + 32]};
-                const float w = wt.w[k];
-                mx = pk_fma(w, a, mx);
-                my = pk_fma(w, b, my);
-                mxx = pk_fma(w, a * a, mxx);
-                myy = pk_fma(w, b * b, myy);
-                mxy = pk_fma(w, a * b, mxy);
-            }
-            hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
-        }
+        ss_hpass_moments(wt, s1, s2, hs, p, q);
         __syncthreads();
         f2 m4[4][5];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int k = 0; k < 5; k++) m4[i][k] = f2{0.f, 0.f};
-#pragma unroll
-        for (int rr = 0; rr < 14; rr++) {
-            f2 v[5];
-#pragma unroll
-            for (int k = 0; k < 5; k++) v[k] = hs[k][4 * q + rr][p];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int tap = rr - i;
-                if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                for (int k = 0; k < 5; k++) m4[i][k] = pk_fma(wt.w[tap], v[k], m4[i][k]);
-            }
-        }
+        ss_vpass(wt, hs, p, q, m4);
         // this thread's 8 pixels (float: 8 terms of at most 1; the sums over threads and tiles are double)
         float ssim8 = 0.f, l18 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int y = cur.at.y0 + 4 * q + i;
-            if (y >= g.H) break;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int x = cur.at.x0 + p + 32 * h;
-                if (x >= g.W) continue;
-                const float mu1 = m4[i][0][h], mu2 = m4[i][1][h];
-                const float s11 = m4[i][2][h] - mu1 * mu1, s22 = m4[i][3][h] - mu2 * mu2;
-                const float s12 = m4[i][4][h] - mu1 * mu2;
-                const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
-                const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
-                const float inv = 1.f / (Cc * D);
-                const float val = A * B * inv;
-                const int c = (4 * q + i + SS_R) * SS_LS + p + 32 * h + SS_R;  // the pixel itself in the halo
-                ssim8 += val;
-                l18 += fabsf(s1[c] - s2[c]);
-                if (dA) {
-                    const size_t o = cur.at.plane + (size_t)y * g.W + x;
-                    const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
-                    const float f_s11 = -val * Cc * inv;
-                    const float f_s12 = 2.f * A * inv;
-                    dA[o] = f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12;
-                    dB[o] = f_s11;
-                    dC[o] = f_s12;
-                }
+        ss_pixels(g, cur.at.x0, cur.at.y0, p, q, [&](int i, int h, int y, int x) {
+            float d[3];
+            const float val = ss_pixel(m4[i], h, C1, C2, dA != nullptr, d);
+            const int c = (4 * q + i + SS_R) * SS_LS + p + 32 * h + SS_R;  // the pixel itself in the halo
+            ssim8 += val;
+            l18 += fabsf(s1[c] - s2[c]);
+            if (dA) {
+                const size_t o = cur.at.plane + (size_t)y * g.W + x;
+                dA[o] = d[0];
+                dB[o] = d[1];
+                dC[o] = d[2];
             }
-        }
-        const double sum_ssim = wave_sum((double)ssim8), sum_l1 = wave_sum((double)l18);
-        if ((threadIdx.x & 63) == 0) {
-            red[threadIdx.x >> 6][0] = sum_ssim;
-            red[threadIdx.x >> 6][1] = sum_l1;
-        }
+        });
+        red_put(red, 0, (double)ssim8);
+        red_put(red, 1, (double)l18);
         __syncthreads();
-        if (threadIdx.x == 0)
-            partial[t] = double2{((red[0][0] + red[1][0]) + red[2][0]) + red[3][0],
-                                 ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]};
+        if (threadIdx.x == 0) partial[t] = double2{red_total(red, 0), red_total(red, 1)};
     }
 }
 
@@ -431,16 +448,12 @@ __global__ void __launch_bounds__(256) photo_loss_reduce_kernel(const double2* p
         sum_ssim += e.x;
         sum_l1 += e.y;
     }
-    sum_ssim = wave_sum(sum_ssim);
-    sum_l1 = wave_sum(sum_l1);
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6][0] = sum_ssim;
-        red[threadIdx.x >> 6][1] = sum_l1;
-    }
+    red_put(red, 0, sum_ssim);
+    red_put(red, 1, sum_l1);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double ssim = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) * inv_n;
-        const double l1 = (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]) * inv_n;
+        const double ssim = red_total(red, 0) * inv_n;
+        const double l1 = red_total(red, 1) * inv_n;
         loss[blockIdx.x] = (float)((1.0 - lambda) * l1 + lambda * (1.0 - ssim));
     }
 }
@@ -463,77 +476,26 @@ __global__ void __launch_bounds__(256) photo_loss_bwd_kernel(SsGrid g, PhotoView
     for (; t < g.ntiles; t += gridDim.x) {
         const PhotoTile cur = photo_tile(g, pv, img, t);
         const float gv = dloss[cur.v];
-        // this thread's output pixels' img / gt values
-        float i1[4][2], i2[4][2];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int y = cur.at.y0 + 4 * q + j, x = cur.at.x0 + p + 32 * h;
-                const size_t o = (y < g.H && x < g.W) ? (size_t)y * g.W + x : 0;
-                i1[j][h] = cur.img[o];
-                i2[j][h] = cur.gt[o];
-            }
-        }
+        float i1[4][2], i2[4][2];  // this thread's output pixels' img / gt values
+        ss_load_pixels(cur.img, cur.gt, g, cur.at.x0, cur.at.y0, p, q, i1, i2);
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SS_STAGE_IT; j++) {
-            const int i = threadIdx.x + j * 256;
-            if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+        ss_stage([&](int i, int j) {
             gs[0][i] = halo.get(0, j);
             gs[1][i] = halo.get(1, j);
             gs[2][i] = halo.get(2, j);
-        }
+        });
         if (t + (int)gridDim.x < g.ntiles) halo.load(src, g, ss_tile(g, t + gridDim.x));
         __syncthreads();
-        for (int r = q; r < SS_HH; r += 8) {
-            f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-            for (int k = 0; k < 11; k++) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float* row = gs[c] + r * SS_LS + p;
-                    s[c] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[c]);
-                }
-            }
-            hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
-        }
+        ss_hpass_planes(wt, gs, hs, p, q);
         __syncthreads();
         f2 s4[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) s4[i][c] = f2{0.f, 0.f};
-#pragma unroll
-        for (int rr = 0; rr < 14; rr++) {
-            f2 v[3];
-#pragma unroll
-            for (int c = 0; c < 3; c++) v[c] = hs[c][4 * q + rr][p];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int tap = rr - i;
-                if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                for (int c = 0; c < 3; c++) s4[i][c] = pk_fma(wt.w[tap], v[c], s4[i][c]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int y = cur.at.y0 + 4 * q + j;
-            if (y >= g.H) break;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int x = cur.at.x0 + p + 32 * h;
-                if (x >= g.W) continue;
-                const float raw = i1[j][h], gt = i2[j][h];
-                const float xv = clamp ? clamp01(raw) : raw;
-                const bool pass = !clamp || (raw >= 0.f && raw <= 1.f);  // torch's clamp backward
-                const float d = xv - gt;
-                const float sgn = (float)((d > 0.f) - (d < 0.f));
-                const float ssim = s4[j][0][h] + 2.f * xv * s4[j][1][h] + gt * s4[j][2][h];
-                dimg[cur.at.plane + (size_t)y * g.W + x] = pass ? gv * (k_ssim * ssim + k_l1 * sgn) : 0.f;
-            }
-        }
+        ss_vpass(wt, hs, p, q, s4);
+        ss_pixels(g, cur.at.x0, cur.at.y0, p, q, [&](int j, int h, int y, int x) {
+            const float raw = i1[j][h];
+            dimg[cur.at.plane + (size_t)y * g.W + x] =
+                clamp_passes(clamp, raw) ? photo_bwd_pixel(s4[j], h, clamped(clamp, raw), i2[j][h], gv, k_ssim, k_l1)
+                                         : 0.f;
+        });
     }
 }
 
@@ -559,9 +521,9 @@ struct VlTile {
 
 __device__ __forceinline__ VlTile vl_tile(const SsGrid& g, int C, int groups, int t)
 {
-    const int x = t % g.tx, r = t / g.tx, y = r % g.ty, z = r / g.ty;
-    const int v = z / groups, c0 = 3 * (z - v * groups);
-    return {v, c0, C - c0 < 3 ? C - c0 : 3, x * SS_TW, y * SS_TH, ((size_t)v * C + c0) * g.H * g.W};
+    const SsTile a = ss_tile(g, t);  // its planes are the channel groups
+    const int v = a.z / groups, c0 = 3 * (a.z - v * groups);
+    return {v, c0, C - c0 < 3 ? C - c0 : 3, a.x0, a.y0, ((size_t)v * C + c0) * g.H * g.W};
 }
 
 // Column c of a view's exposure: e_c = k[0] raw_0 + k[1] raw_1 + k[2] raw_2 + off (uniform: scalar loads).
@@ -655,7 +617,9 @@ struct VlHalo {
     }
 };
 
-// ... and of the backward's three partial planes of one channel
+// ... and of the backward's three partial planes of one channel: SsHalo<3> in vl_ld's addressing and with
+// vl_tid().  Not one template: in this addressing all six kernels keep 0 scratch and 2 waves/SIMD
+// (ssim_bwd_kernel 182 VGPRs for 202), but ssim_fwd_kernel / ssim_bwd_kernel ran 2.7 % / 4.9 % slower at 1080p.
 struct VlHalo3 {
     float v[3][SS_STAGE_IT];
     uint32_t outside;
@@ -690,29 +654,22 @@ view_loss_fwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, floa
     int t = blockIdx.x;
     // the inverse-depth tiles (tile t of view t / (tx ty)): no window, one double each
     for (; t < depth_tiles; t += gridDim.x) {
-        const int tx0 = (t % g.tx) * SS_TW, r = t / g.tx, ty0 = (r % g.ty) * SS_TH, v = r / g.ty;
-        const float* tg = a.target[v];
+        const SsTile dt = ss_tile(g, t);  // its planes are the views
+        const float* tg = a.target[dt.z];
         float d8 = 0.f;
         if (tg) {
-            const float* dm = a.dmask[v];
-            const float* inv = a.invdepth + (size_t)v * hw;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int y = ty0 + 4 * q + i, x = tx0 + p + 32 * h;
-                    if (y >= g.H || x >= g.W) continue;
-                    const size_t o = (size_t)y * g.W + x;
-                    const float d = inv[o] - tg[o];
-                    d8 += fabsf(dm ? d * dm[o] : d);
-                }
-            }
+            const float* dm = a.dmask[dt.z];
+            const float* inv = a.invdepth + dt.plane;
+            ss_pixels(g, dt.x0, dt.y0, p, q, [&](int, int, int y, int x) {
+                const size_t o = (size_t)y * g.W + x;
+                const float d = inv[o] - tg[o];
+                d8 += fabsf(dm ? d * dm[o] : d);
+            });
         }
-        const double sum = wave_sum((double)d8);
         __syncthreads();  // the previous tile is done with red
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = sum;
+        red_put(red, 0, (double)d8);
         __syncthreads();
-        if (threadIdx.x == 0) dpartial[t] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+        if (threadIdx.x == 0) dpartial[t] = red_total(red, 0);
     }
     if (t >= g.ntiles) return;  // uniform over the workgroup
     VlHalo halo;
@@ -729,15 +686,12 @@ view_loss_fwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, floa
         for (int c = 0; c < cur.nc; c++) {  // uniform
             const VlColumn E = vl_column(a.exposure, cur.v, c);
             __syncthreads();  // the previous channel is done with s1, s2, hs and red
-#pragma unroll
-            for (int j = 0; j < SS_STAGE_IT; j++) {
-                const int i = threadIdx.x + j * 256;
-                if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+            ss_stage([&](int i, int j) {
                 const bool out = (halo.outside >> j) & 1;
                 const float e = vl_expose(a.exposure != nullptr, E, c, halo.raw[0][j], halo.raw[1][j], halo.raw[2][j]);
-                s1[i] = out ? 0.f : (a.clamp ? clamp01(e) : e) * halo.m[j];
+                s1[i] = out ? 0.f : clamped(a.clamp, e) * halo.m[j];
                 s2[i] = out ? 0.f : halo.gt[j];
-            }
+            });
             // the next channel's ground truth, or the next tile
             if (c + 1 < cur.nc) {
                 halo.load_gt(g, a, cur, c + 1);
@@ -747,83 +701,31 @@ view_loss_fwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, floa
                 halo.load_gt(g, a, n, 0);
             }
             __syncthreads();
-            for (int r = q; r < SS_HH; r += 8) {
-                f2 mx = {0.f, 0.f}, my = mx, mxx = mx, myy = mx, mxy = mx;
-                const float* r1 = s1 + r * SS_LS + p;
-                const float* r2 = s2 + r * SS_LS + p;
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-                    const f2 xa = {r1[k], r1[k + 32]}, xb = {r2[k], r2[k + 32]};
-                    const float w = wt.w[k];
-                    mx = pk_fma(w, xa, mx);
-                    my = pk_fma(w, xb, my);
-                    mxx = pk_fma(w, xa * xa, mxx);
-                    myy = pk_fma(w, xb * xb, myy);
-                    mxy = pk_fma(w, xa * xb, mxy);
-                }
-                hs[0][r][p] = mx; hs[1][r][p] = my; hs[2][r][p] = mxx; hs[3][r][p] = myy; hs[4][r][p] = mxy;
-            }
+            ss_hpass_moments(wt, s1, s2, hs, p, q);
             __syncthreads();
             f2 m4[4][5];
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int k = 0; k < 5; k++) m4[i][k] = f2{0.f, 0.f};
-#pragma unroll
-            for (int rr = 0; rr < 14; rr++) {
-                f2 v[5];
-#pragma unroll
-                for (int k = 0; k < 5; k++) v[k] = hs[k][4 * q + rr][p];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int tap = rr - i;
-                    if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                    for (int k = 0; k < 5; k++) m4[i][k] = pk_fma(wt.w[tap], v[k], m4[i][k]);
-                }
-            }
+            ss_vpass(wt, hs, p, q, m4);
             // (the pixels' coordinates and offsets recomputed per channel, not kept across the window passes)
             const int et = vl_tid(), ep = et & 31, eq = et >> 5;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int y = cur.y0 + 4 * eq + i;
-                if (y >= g.H) break;
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const int x = cur.x0 + ep + 32 * h;
-                    if (x >= g.W) continue;
-                    const float mu1 = m4[i][0][h], mu2 = m4[i][1][h];
-                    const float s11 = m4[i][2][h] - mu1 * mu1, s22 = m4[i][3][h] - mu2 * mu2;
-                    const float s12 = m4[i][4][h] - mu1 * mu2;
-                    const float A = 2.f * mu1 * mu2 + C1, B = 2.f * s12 + C2;
-                    const float Cc = mu1 * mu1 + mu2 * mu2 + C1, D = s11 + s22 + C2;
-                    const float inv = 1.f / (Cc * D);
-                    const float val = A * B * inv;
-                    const int ci = (4 * eq + i + SS_R) * SS_LS + ep + 32 * h + SS_R;  // the pixel itself in the halo
-                    ssim8 += val;
-                    l18 += fabsf(s1[ci] - s2[ci]);
-                    if (dA) {
-                        const size_t pl = cur.plane0 + c * hw;
-                        const uint32_t o = 4u * ((uint32_t)y * (uint32_t)g.W + (uint32_t)x);
-                        const float f_mu1 = 2.f * inv * (mu2 * B - mu1 * val * D);
-                        const float f_s11 = -val * Cc * inv;
-                        const float f_s12 = 2.f * A * inv;
-                        vl_st(dA + pl, o, f_mu1 - 2.f * mu1 * f_s11 - mu2 * f_s12);
-                        vl_st(dB + pl, o, f_s11);
-                        vl_st(dC + pl, o, f_s12);
-                    }
+            ss_pixels(g, cur.x0, cur.y0, ep, eq, [&](int i, int h, int y, int x) {
+                float d[3];
+                const float val = ss_pixel(m4[i], h, C1, C2, dA != nullptr, d);
+                const int ci = (4 * eq + i + SS_R) * SS_LS + ep + 32 * h + SS_R;  // the pixel itself in the halo
+                ssim8 += val;
+                l18 += fabsf(s1[ci] - s2[ci]);
+                if (dA) {
+                    const size_t pl = cur.plane0 + c * hw;
+                    const uint32_t o = 4u * ((uint32_t)y * (uint32_t)g.W + (uint32_t)x);
+                    vl_st(dA + pl, o, d[0]);
+                    vl_st(dB + pl, o, d[1]);
+                    vl_st(dC + pl, o, d[2]);
                 }
-            }
+            });
         }
-        const double sum_ssim = wave_sum((double)ssim8), sum_l1 = wave_sum((double)l18);
-        if ((threadIdx.x & 63) == 0) {
-            red[threadIdx.x >> 6][0] = sum_ssim;
-            red[threadIdx.x >> 6][1] = sum_l1;
-        }
+        red_put(red, 0, (double)ssim8);
+        red_put(red, 1, (double)l18);
         __syncthreads();
-        if (threadIdx.x == 0)
-            partial[t - depth_tiles] = double2{((red[0][0] + red[1][0]) + red[2][0]) + red[3][0],
-                                               ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]};
+        if (threadIdx.x == 0) partial[t - depth_tiles] = double2{red_total(red, 0), red_total(red, 1)};
     }
 }
 
@@ -845,19 +747,14 @@ __global__ void __launch_bounds__(256) view_loss_reduce_kernel(const double2* pa
     if (dpartial)
         for (int k = threadIdx.x; k < depth_tiles_per_view; k += 256)
             sum_d += dpartial[(size_t)blockIdx.x * depth_tiles_per_view + k];
-    sum_ssim = wave_sum(sum_ssim);
-    sum_l1 = wave_sum(sum_l1);
-    sum_d = wave_sum(sum_d);
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6][0] = sum_ssim;
-        red[threadIdx.x >> 6][1] = sum_l1;
-        red[threadIdx.x >> 6][2] = sum_d;
-    }
+    red_put(red, 0, sum_ssim);
+    red_put(red, 1, sum_l1);
+    red_put(red, 2, sum_d);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double ssim = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) * inv_n;
-        const double l1 = (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]) * inv_n;
-        const double depth = (((red[0][2] + red[1][2]) + red[2][2]) + red[3][2]) * depth_scale;
+        const double ssim = red_total(red, 0) * inv_n;
+        const double l1 = red_total(red, 1) * inv_n;
+        const double depth = red_total(red, 2) * depth_scale;
         loss[blockIdx.x] = (float)((1.0 - lambda) * l1 + lambda * (1.0 - ssim) + depth);
     }
 }
@@ -878,27 +775,21 @@ view_loss_bwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, Ssim
     const size_t hw = (size_t)g.H * g.W;
     int t = blockIdx.x;
     for (; t < depth_tiles; t += gridDim.x) {
-        const int tx0 = (t % g.tx) * SS_TW, r = t / g.tx, ty0 = (r % g.ty) * SS_TH, v = r / g.ty;
-        const float* tg = a.target[v];
-        const float* dm = a.dmask[v];
-        const float* inv = a.invdepth + (size_t)v * hw;
-        const float gv = dloss[v] * k_depth;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int y = ty0 + 4 * q + i, x = tx0 + p + 32 * h;
-                if (y >= g.H || x >= g.W) continue;
-                const size_t o = (size_t)y * g.W + x;
-                float out = 0.f;
-                if (tg) {
-                    const float w = dm ? dm[o] : 1.f;
-                    const float d = (inv[o] - tg[o]) * w;
-                    out = gv * (float)((d > 0.f) - (d < 0.f)) * w;
-                }
-                dinv[(size_t)v * hw + o] = out;
+        const SsTile dt = ss_tile(g, t);  // its planes are the views
+        const float* tg = a.target[dt.z];
+        const float* dm = a.dmask[dt.z];
+        const float* inv = a.invdepth + dt.plane;
+        const float gv = dloss[dt.z] * k_depth;
+        ss_pixels(g, dt.x0, dt.y0, p, q, [&](int, int, int y, int x) {
+            const size_t o = (size_t)y * g.W + x;
+            float out = 0.f;
+            if (tg) {
+                const float w = dm ? dm[o] : 1.f;
+                const float d = (inv[o] - tg[o]) * w;
+                out = gv * (float)((d > 0.f) - (d < 0.f)) * w;
             }
-        }
+            dinv[dt.plane + o] = out;
+        });
     }
     if (t >= g.ntiles) return;  // uniform over the workgroup
     VlHalo3 halo;
@@ -938,14 +829,11 @@ view_loss_bwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, Ssim
                 for (int h = 0; h < 2; h++) gt8[j][h] = vl_ld(gtv + c * hw, off[j][h]);
             }
             __syncthreads();  // the previous channel is done with gs, hs and red
-#pragma unroll
-            for (int j = 0; j < SS_STAGE_IT; j++) {
-                const int i = threadIdx.x + j * 256;
-                if (j == SS_STAGE_IT - 1 && i >= SS_STAGE) break;
+            ss_stage([&](int i, int j) {
                 gs[0][i] = halo.get(0, j);
                 gs[1][i] = halo.get(1, j);
                 gs[2][i] = halo.get(2, j);
-            }
+            });
             // the next channel's planes, or the next tile's first
             if (c + 1 < cur.nc) {
                 const size_t pl = cur.plane0 + (c + 1) * hw;
@@ -955,50 +843,21 @@ view_loss_bwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, Ssim
                 halo.load(dA + n.plane0, dB + n.plane0, dC + n.plane0, g, n.x0, n.y0);
             }
             __syncthreads();
-            for (int r = q; r < SS_HH; r += 8) {
-                f2 s[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-                for (int k = 0; k < 11; k++) {
-#pragma unroll
-                    for (int n = 0; n < 3; n++) {
-                        const float* row = gs[n] + r * SS_LS + p;
-                        s[n] = pk_fma(wt.w[k], f2{row[k], row[k + 32]}, s[n]);
-                    }
-                }
-                hs[0][r][p] = s[0]; hs[1][r][p] = s[1]; hs[2][r][p] = s[2];
-            }
+            ss_hpass_planes(wt, gs, hs, p, q);
             __syncthreads();
             f2 s4[4][3];
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int n = 0; n < 3; n++) s4[i][n] = f2{0.f, 0.f};
-#pragma unroll
-            for (int rr = 0; rr < 14; rr++) {
-                f2 v[3];
-#pragma unroll
-                for (int n = 0; n < 3; n++) v[n] = hs[n][4 * q + rr][p];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int tap = rr - i;
-                    if (tap < 0 || tap > 10) continue;
-#pragma unroll
-                    for (int n = 0; n < 3; n++) s4[i][n] = pk_fma(wt.w[tap], v[n], s4[i][n]);
-                }
-            }
+            ss_vpass(wt, hs, p, q, s4);
             float es[4] ={0.f, 0.f, 0.f, 0.f};  // this thread's sums of raw_k g_c and of g_c
 #pragma unroll
             for (int j = 0; j < 4; j++) {
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
-                    const float m = mk[j][h], gt = gt8[j][h];
+                    const float m = mk[j][h];
                     const float e = vl_expose(a.exposure != nullptr, E, c, rw[0][j][h], rw[1][j][h], rw[2][j][h]);
-                    const bool pass = !a.clamp || (e >= 0.f && e <= 1.f);  // torch's clamp backward
-                    const float xv = (a.clamp ? clamp01(e) : e) * m;
-                    const float d = xv - gt;
-                    const float sgn = (float)((d > 0.f) - (d < 0.f));
-                    const float ssim = s4[j][0][h] + 2.f * xv * s4[j][1][h] + gt * s4[j][2][h];
-                    const float gc = pass ? m * (gv * (k_ssim * ssim + k_l1 * sgn)) : 0.f;
+                    const float gc =
+                        clamp_passes(a.clamp, e)
+                            ? m * photo_bwd_pixel(s4[j], h, clamped(a.clamp, e) * m, gt8[j][h], gv, k_ssim, k_l1)
+                            : 0.f;
 #pragma unroll
                     for (int k = 0; k < 3; k++) {
                         draw[k][j][h] += E.k[k] * gc;
@@ -1009,31 +868,17 @@ view_loss_bwd_kernel(SsGrid g, ViewLossArgs a, int groups, int depth_tiles, Ssim
             }
             if (a.exposure) {  // uniform; red is read after the channel loop
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const double s = wave_sum((double)es[k]);
-                    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k < 3 ? 4 * k + c : 4 * c + 3] = s;
-                }
+                for (int k = 0; k < 4; k++) red_put(red, k < 3 ? 4 * k + c : 4 * c + 3, (double)es[k]);
             }
         }
+        ss_pixels(g, cur.x0, cur.y0, p, q, [&](int j, int h, int, int) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int y = cur.y0 + 4 * q + j;
-            if (y >= g.H) break;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int x = cur.x0 + p + 32 * h;
-                if (x >= g.W) continue;
-#pragma unroll
-                for (int k = 0; k < 3; k++)
-                    if (k < cur.nc)
-                        vl_st(dimg + cur.plane0 + k * hw, off[j][h], draw[k][j][h]);
-            }
-        }
+            for (int k = 0; k < 3; k++)
+                if (k < cur.nc) vl_st(dimg + cur.plane0 + k * hw, off[j][h], draw[k][j][h]);
+        });
         if (a.exposure) {  // uniform
             __syncthreads();
-            if (threadIdx.x < 12)
-                epartial[(size_t)(t - depth_tiles) * 12 + threadIdx.x] =
-                    ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+            if (threadIdx.x < 12) epartial[(size_t)(t - depth_tiles) * 12 + threadIdx.x] = red_total(red, threadIdx.x);
         }
     }
 }
@@ -1052,14 +897,9 @@ __global__ void __launch_bounds__(256) view_loss_exposure_reduce_kernel(const do
         for (int n = 0; n < 12; n++) s[n] += pv[(size_t)k * 12 + n];
     }
 #pragma unroll
-    for (int n = 0; n < 12; n++) {
-        const double w = wave_sum(s[n]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][n] = w;
-    }
+    for (int n = 0; n < 12; n++) red_put(red, n, s[n]);
     __syncthreads();
-    if (threadIdx.x < 12)
-        dexposure[blockIdx.x * 12 + threadIdx.x] =
-            (float)(((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x]);
+    if (threadIdx.x < 12) dexposure[blockIdx.x * 12 + threadIdx.x] = (float)red_total(red, threadIdx.x);
 }
 
 // The reference's window (utils/loss_utils.py:46-53): exp in double, stored as float32,
@@ -1076,38 +916,63 @@ static SsimWeights ssim_weights()
     return w;
 }
 
-static hipError_t ssim_grid(int planes, int H, int W, SsGrid* g, int* blocks)
+// What every launch starts from: the tile grid of n0 * n1 planes of H x W and the workgroup count of
+// the persistent grid.  blocks == 0 with hipSuccess: an empty problem, nothing to launch.
+struct SsPlan {
+    SsGrid g;
+    int blocks;
+};
+
+static hipError_t ss_plan(int n0, int n1, int H, int W, SsPlan* p)
 {
-    g->H = H;
-    g->W = W;
-    g->tx = (W + SS_TW - 1) / SS_TW;
-    g->ty = (H + SS_TH - 1) / SS_TH;
-    const long n = (long)g->tx * g->ty * planes;
+    p->blocks = 0;
+    if (n0 <= 0 || n1 <= 0 || H <= 0 || W <= 0) return hipSuccess;
+    if ((size_t)n0 * n1 > 0x7FFFFFFFu) return hipErrorInvalidValue;
+    SsGrid& g = p->g;
+    g.H = H;
+    g.W = W;
+    g.tx = (W + SS_TW - 1) / SS_TW;
+    g.ty = (H + SS_TH - 1) / SS_TH;
+    const long n = (long)g.tx * g.ty * (n0 * n1);
     if (n > 0x7FFFFFFF) return hipErrorInvalidValue;
-    g->ntiles = (int)n;
+    g.ntiles = (int)n;
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
     const long b = (long)(cus > 0 ? cus : 1) * SS_BLOCKS_PER_CU;
-    *blocks = (int)(b < n ? b : n);
+    p->blocks = (int)(b < n ? b : n);
     return hipSuccess;
+}
+
+// The loss kernels' SSIM constants (the map kernels take their caller's) and, for views of C H W
+// elements, the factors of the loss and of its gradient.
+constexpr float SS_C1 = (float)(0.01 * 0.01), SS_C2 = (float)(0.03 * 0.03);
+
+struct LossScale {
+    double inv_n, depth;  // 1 / (C H W); depth_weight / (H W)
+    float k_ssim, k_l1, k_depth;
+};
+
+static LossScale loss_scale(int C, int H, int W, float lambda, float depth_weight)
+{
+    const double n = (double)C * H * W;
+    const double depth = (double)depth_weight / ((double)H * W);
+    return {1.0 / n, depth, (float)(-(double)lambda / n), (float)((1.0 - (double)lambda) / n), (float)depth};
 }
 
 hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const float* img1, const float* img2,
                            float* map, float* dA, float* dB, float* dC, hipStream_t s)
 {
-    if (planes <= 0 || H <= 0 || W <= 0) return hipSuccess;
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(planes, H, W, &g, &blocks);
-    if (e != hipSuccess) return e;
+    SsPlan pl;
+    const hipError_t e = ss_plan(planes, 1, H, W, &pl);
+    if (e != hipSuccess || !pl.blocks) return e;
     const SsimWeights w = ssim_weights();
     if (dA && dB && dC)
-        hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, g, C1, C2, w, img1, img2, map, dA,
-                           dB, dC);
+        hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3(pl.blocks), dim3(256), 0, s, pl.g, C1, C2, w, img1, img2, map,
+                           dA, dB, dC);
     else
-        hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, g, C1, C2, w, img1, img2, map,
+        hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3(pl.blocks), dim3(256), 0, s, pl.g, C1, C2, w, img1, img2, map,
                            dA, dB, dC);
     return hipGetLastError();
 }
@@ -1115,13 +980,11 @@ hipError_t launch_ssim_fwd(int planes, int H, int W, float C1, float C2, const f
 hipError_t launch_ssim_bwd(int planes, int H, int W, const float* img1, const float* img2, const float* dmap,
                            const float* dA, const float* dB, const float* dC, float* dimg1, hipStream_t s)
 {
-    if (planes <= 0 || H <= 0 || W <= 0) return hipSuccess;
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(planes, H, W, &g, &blocks);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, ssim_weights(), img1, img2, dmap, dA, dB,
-                       dC, dimg1);
+    SsPlan pl;
+    const hipError_t e = ss_plan(planes, 1, H, W, &pl);
+    if (e != hipSuccess || !pl.blocks) return e;
+    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(pl.blocks), dim3(256), 0, s, pl.g, ssim_weights(), img1, img2, dmap, dA,
+                       dB, dC, dimg1);
     return hipGetLastError();
 }
 
@@ -1140,21 +1003,17 @@ hipError_t launch_photo_loss_fwd(const PhotoViews& views, int H, int W, float la
                                  float* loss, float* dA, float* dB, float* dC, void* workspace, hipStream_t s)
 {
     const int V = views.V, C = views.C;
-    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
-    if ((size_t)V * C > 0x7FFFFFFFu) return hipErrorInvalidValue;
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(V * C, H, W, &g, &blocks);
-    if (e != hipSuccess) return e;
+    SsPlan pl;
+    hipError_t e = ss_plan(V, C, H, W, &pl);
+    if (e != hipSuccess || !pl.blocks) return e;
     const bool train = dA && dB && dC;
     double2* partial = static_cast<double2*>(workspace);
-    hipLaunchKernelGGL(photo_loss_fwd_kernel, dim3(blocks), dim3(256), 0, s, g, views, (float)(0.01 * 0.01),
-                       (float)(0.03 * 0.03), ssim_weights(), clamp ? 1 : 0, img, train ? dA : nullptr, dB, dC, partial);
+    hipLaunchKernelGGL(photo_loss_fwd_kernel, dim3(pl.blocks), dim3(256), 0, s, pl.g, views, SS_C1, SS_C2,
+                       ssim_weights(), clamp ? 1 : 0, img, train ? dA : nullptr, dB, dC, partial);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const double n = (double)C * H * W;
     hipLaunchKernelGGL(photo_loss_reduce_kernel, dim3(V), dim3(256), 0, s, partial, (int)photo_tiles_per_view(C, H, W),
-                       1.0 / n, (double)lambda, loss);
+                       loss_scale(C, H, W, lambda, 0.f).inv_n, (double)lambda, loss);
     return hipGetLastError();
 }
 
@@ -1162,16 +1021,12 @@ hipError_t launch_photo_loss_bwd(const PhotoViews& views, int H, int W, float la
                                  const float* dloss, const float* dA, const float* dB, const float* dC, float* dimg,
                                  hipStream_t s)
 {
-    const int V = views.V, C = views.C;
-    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
-    if ((size_t)V * C > 0x7FFFFFFFu) return hipErrorInvalidValue;
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(V * C, H, W, &g, &blocks);
-    if (e != hipSuccess) return e;
-    const double n = (double)C * H * W;
-    hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, views, ssim_weights(), clamp ? 1 : 0,
-                       (float)(-(double)lambda / n), (float)((1.0 - (double)lambda) / n), img, dloss, dA, dB, dC, dimg);
+    SsPlan pl;
+    const hipError_t e = ss_plan(views.V, views.C, H, W, &pl);
+    if (e != hipSuccess || !pl.blocks) return e;
+    const LossScale k = loss_scale(views.C, H, W, lambda, 0.f);
+    hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3(pl.blocks), dim3(256), 0, s, pl.g, views, ssim_weights(),
+                       clamp ? 1 : 0, k.k_ssim, k.k_l1, img, dloss, dA, dB, dC, dimg);
     return hipGetLastError();
 }
 
@@ -1207,21 +1062,20 @@ hipError_t launch_view_loss_fwd(const ViewLossArgs& a, int H, int W, float lambd
     if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return hipSuccess;
     const VlShape sh = view_loss_shape(a, H, W);
     if ((size_t)V * (sh.groups + 1) > 0x7FFFFFFFu) return hipErrorInvalidValue;
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(V * (sh.groups + (sh.depth ? 1 : 0)), H, W, &g, &blocks);
+    SsPlan pl;
+    hipError_t e = ss_plan(V, sh.groups + (sh.depth ? 1 : 0), H, W, &pl);
     if (e != hipSuccess) return e;
     const bool train = dA && dB && dC;
+    const LossScale k = loss_scale(C, H, W, lambda, a.depth_weight);
     double2* partial = static_cast<double2*>(workspace);
     double* dpartial = static_cast<double*>(workspace) + 2 * (size_t)V * sh.groups * sh.txy;
-    hipLaunchKernelGGL(view_loss_fwd_kernel, dim3(blocks), dim3(256), 0, s, g, a, sh.groups,
-                       sh.depth ? (int)(V * sh.txy) : 0, (float)(0.01 * 0.01), (float)(0.03 * 0.03), ssim_weights(), img,
-                       train ? dA : nullptr, dB, dC, partial, dpartial);
+    hipLaunchKernelGGL(view_loss_fwd_kernel, dim3(pl.blocks), dim3(256), 0, s, pl.g, a, sh.groups,
+                       sh.depth ? (int)(V * sh.txy) : 0, SS_C1, SS_C2, ssim_weights(), img, train ? dA : nullptr, dB, dC,
+                       partial, dpartial);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(view_loss_reduce_kernel, dim3(V), dim3(256), 0, s, partial, (int)(sh.groups * sh.txy),
-                       sh.depth ? dpartial : nullptr, (int)sh.txy, 1.0 / ((double)C * H * W), (double)lambda,
-                       (double)a.depth_weight / ((double)H * W), loss);
+                       sh.depth ? dpartial : nullptr, (int)sh.txy, k.inv_n, (double)lambda, k.depth, loss);
     return hipGetLastError();
 }
 
@@ -1238,16 +1092,14 @@ hipError_t launch_view_loss_bwd(const ViewLossArgs& a, int H, int W, float lambd
         const hipError_t z = hipMemsetAsync(dinv, 0, (size_t)V * H * W * sizeof(float), s);
         if (z != hipSuccess) return z;
     }
-    SsGrid g;
-    int blocks;
-    hipError_t e = ssim_grid(V * (sh.groups + (depth ? 1 : 0)), H, W, &g, &blocks);
+    SsPlan pl;
+    hipError_t e = ss_plan(V, sh.groups + (depth ? 1 : 0), H, W, &pl);
     if (e != hipSuccess) return e;
-    const double n = (double)C * H * W;
+    const LossScale k = loss_scale(C, H, W, lambda, a.depth_weight);
     double* epartial = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(view_loss_bwd_kernel, dim3(blocks), dim3(256), 0, s, g, a, sh.groups,
-                       depth ? (int)(V * sh.txy) : 0, ssim_weights(), (float)(-(double)lambda / n),
-                       (float)((1.0 - (double)lambda) / n), (float)((double)a.depth_weight / ((double)H * W)), img, dloss,
-                       dA, dB, dC, dimg, dinv, epartial);
+    hipLaunchKernelGGL(view_loss_bwd_kernel, dim3(pl.blocks), dim3(256), 0, s, pl.g, a, sh.groups,
+                       depth ? (int)(V * sh.txy) : 0, ssim_weights(), k.k_ssim, k.k_l1, k.k_depth, img, dloss, dA, dB, dC,
+                       dimg, dinv, epartial);
     e = hipGetLastError();
     if (e != hipSuccess || !a.exposure) return e;
     hipLaunchKernelGGL(view_loss_exposure_reduce_kernel, dim3(V), dim3(256), 0, s, epartial, (int)sh.txy, dexposure);

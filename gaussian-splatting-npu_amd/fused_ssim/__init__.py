@@ -118,6 +118,26 @@ def _gt_pointers(gts):
     return (_vp * len(gts))(*[g.data_ptr() for g in gts])
 
 
+def _ground_truths(gt, x, single):
+    """`gt` -- one tensor of img's shape (checked by the caller) or a sequence of V (C,H,W) tensors --
+    as the validated list of V detached contiguous float32 tensors on the device of x, the (V,C,H,W) img."""
+    if torch.is_tensor(gt):
+        gts = [gt] if single else list(gt.unbind(0))
+    else:
+        gts = list(gt)
+    V = x.shape[0]
+    if len(gts) != V:
+        raise RuntimeError(f"{V} views but {len(gts)} ground-truth images")
+    for g in gts:
+        if not torch.is_tensor(g) or g.shape != x.shape[1:]:
+            raise RuntimeError("every ground-truth image must have the shape of one view of img")
+        if g.device != x.device or g.dtype != torch.float32:
+            raise RuntimeError(f"ground-truth images must be float32 on {x.device}")
+    if x.numel() == 0:
+        raise RuntimeError("img is empty")
+    return [g.detach().contiguous() for g in gts]
+
+
 class FusedL1SSIMLoss(torch.autograd.Function):
     """(V,) losses of a contiguous float32 (V,C,H,W) batch against V separate (C,H,W) ground truths.
     `train`: keep the partial planes for a backward."""
@@ -175,26 +195,13 @@ def fused_l1_ssim_loss(img, gt, lambda_dssim=0.2, clamp=False):
     if img.dtype != torch.float32:
         raise RuntimeError(f"img must be float32, got {img.dtype}")
     single = img.dim() == 3
-    if torch.is_tensor(gt):
-        if gt.shape != img.shape:
-            raise RuntimeError("img and gt must have the same shape")
-        gts = [gt] if single else list(gt.unbind(0))
-    else:
-        gts = list(gt)
+    if torch.is_tensor(gt) and gt.shape != img.shape:
+        raise RuntimeError("img and gt must have the same shape")
     x = img[None] if single else img
     V = x.shape[0]
     if not 1 <= V <= MAX_VIEWS:
         raise RuntimeError(f"fused_l1_ssim_loss takes 1 to {MAX_VIEWS} views, got {V}")
-    if len(gts) != V:
-        raise RuntimeError(f"{V} views but {len(gts)} ground-truth images")
-    for g in gts:
-        if not torch.is_tensor(g) or g.shape != x.shape[1:]:
-            raise RuntimeError("every ground-truth image must have the shape of one view of img")
-        if g.device != x.device or g.dtype != torch.float32:
-            raise RuntimeError(f"ground-truth images must be float32 on {x.device}")
-    if x.numel() == 0:
-        raise RuntimeError("img is empty")
-    gts = [g.detach().contiguous() for g in gts]
+    gts = _ground_truths(gt, x, single)
     train = torch.is_grad_enabled() and x.requires_grad
     loss = FusedL1SSIMLoss.apply(x.contiguous(), float(lambda_dssim), bool(clamp), train, *gts)
     return loss[0] if single else loss
@@ -357,19 +364,9 @@ def fused_view_loss(img, gt, lambda_dssim=0.2, clamp=True, exposure=None, alpha_
     depth = invdepth is not None and depth_weight > 0 and any(t is not None for t in targets)
     if exposure is None and not depth and all(m is None for m in masks):
         return fused_l1_ssim_loss(img, gt, lambda_dssim, clamp)
-    gts = [gt] if single and torch.is_tensor(gt) else (list(gt.unbind(0)) if torch.is_tensor(gt) else list(gt))
-    if len(gts) != V:
-        raise RuntimeError(f"{V} views but {len(gts)} ground-truth images")
-    for g in gts:
-        if not torch.is_tensor(g) or g.shape != x.shape[1:]:
-            raise RuntimeError("every ground-truth image must have the shape of one view of img")
-        if g.device != dev or g.dtype != torch.float32:
-            raise RuntimeError(f"ground-truth images must be float32 on {dev}")
-    if x.numel() == 0:
-        raise RuntimeError("img is empty")
+    gts = _ground_truths(gt, x, single)
     if H * W >= 2 ** 30:
         raise RuntimeError("fused_view_loss takes images of fewer than 2^30 pixels")
-    gts = [g.detach().contiguous() for g in gts]
     E = None if exposure is None else (exposure[None] if single else exposure).contiguous()
     inv = invdepth.reshape(V, 1, H, W).contiguous() if depth else None
     if not depth:

@@ -10,7 +10,8 @@ autograd of train.py:112-141 restated per view:
 Tolerances are those of tests/test_photo_loss.py: every loss within 2e-6; every view's dL/draw,
 dL/dinv and dL/dE within 1e-4 of that array's largest reference element.  The shapes are that
 file's, for the same reasons (below one tile, one past a tile edge, an exact tile height, more tiles
-than persistent workgroups).
+than persistent workgroups).  A view tile spans a view's three channels, so at the largest of them no
+workgroup gets a second view tile; MANY_TILES (below) is there for that.
 
 The float32 kernel and the float64 reference must take the same branch of the clamp and of
 sign(x - gt), so threshold pixels are removed by construction: raw is nudged until neither raw nor
@@ -42,6 +43,10 @@ SHAPES = [(3, 37, 29), (2, 3, 33, 65), (3, 3, 64, 80), (2, 3, 300, 600)]
 SMALL = SHAPES[:3]
 IDS = [str(s) for s in SHAPES]
 LAMBDAS = [0.0, 0.2, 1.0]
+# More view tiles (and as many depth tiles) than persistent workgroups, so that a workgroup prefetches
+# its next tile's halo across the tile loop: all extras at one lambda only.
+MANY_TILES = (2, 3, 481, 1025)
+ALL_EXTRAS = [(s, l) for l in LAMBDAS for s in SHAPES] + [(MANY_TILES, 0.2)]
 DEPTH_WEIGHT = 0.7
 EPS, NUDGE = 1e-5, 1e-3
 
@@ -236,9 +241,13 @@ def test_each_extra_alone(shape, extras):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("lam", LAMBDAS)
-@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+@pytest.mark.parametrize("shape,lam", ALL_EXTRAS, ids=[f"{s}-{l}" for s, l in ALL_EXTRAS])
 def test_all_extras(shape, lam):
+    if shape == MANY_TILES:
+        # 16 x 17 tile positions, two views: 544 depth tiles, then 544 view tiles, for a persistent grid
+        # of 2 workgroups per CU, so some workgroups walk a second view tile (prefetched across the tile
+        # loop) and some reach the view tiles on a later round of the depth-tile loop
+        assert 2 * 16 * 17 > 2 * torch.cuda.get_device_properties(0).multi_processor_count
     grads = _check(shape, True, True, True, True, lam)
     _check_exact_zeros(shape, True, True, True, grads)
 
