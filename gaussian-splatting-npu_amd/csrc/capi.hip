@@ -150,11 +150,12 @@ int stream_join(PrefixStream* streams, hipStream_t from, hipStream_t forked)
 // ---------------------------------------------------------------------------
 enum ProfKernel {
     PK_PREPROCESS = 0, PK_DEPTH_SORT, PK_SCAN, PK_EMIT, PK_TILE_SORT, PK_RANGES, PK_RENDER_FWD, PK_RENDER_BWD,
-    PK_PREPROCESS_BWD, PK_TILE_ORDER,
+    PK_PREPROCESS_BWD, PK_TILE_ORDER, PK_CAMERA_BWD,
     PK_COUNT
 };
 const char* kProfNames[PK_COUNT] = {"preprocess_fwd", "depth_sort", "scan", "emit_instances", "tile_sort",
-                                    "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "tile_order"};
+                                    "tile_ranges", "render_fwd", "render_bwd", "preprocess_bwd", "tile_order",
+                                    "camera_bwd"};
 struct Prof {
     bool on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool[PK_COUNT];
@@ -1149,6 +1150,58 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
     {
         ProfScope ps_(PK_PREPROCESS_BWD, s);
         HIP_TRY(launch_preprocess_bwd_views(A, s));
+    }
+    DEBUG_SYNC(s);
+    return GSR_OK;
+}
+
+size_t gsr_camera_grad_workspace_size(int V, int P) { return camera_bwd_workspace_bytes(V, P); }
+
+int gsr_backward_camera_views(int V, int P, int D, int M, const int* R, int width, int height, const float* means3D,
+                              const float* dc, const float* shs, const float* colors_precomp,
+                              const float* opacities, const float* scales, float scale_modifier,
+                              const float* rotations, const float* cov3D_precomp, const float* const* viewmatrices,
+                              const float* const* projmatrices, const float* const* campos, const float* tan_fovx,
+                              const float* tan_fovy, char* const* geom_buffers, char* const* binning_buffers,
+                              bool has_invdepth, bool antialiasing, char* workspace, float* dL_dviewmatrix,
+                              float* dL_dprojmatrix, float* dL_dcampos, bool debug, gsr_stream_t stream)
+{
+    if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
+    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (!workspace || !dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
+        return fail(GSR_ERR_INVALID, "null workspace or camera gradient");
+    if (dc && colors_precomp)
+        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
+    if (dc && M > 0 && !shs) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs NULL");
+    if (!R || !viewmatrices || !projmatrices || !campos || !tan_fovx || !tan_fovy || !geom_buffers ||
+        !binning_buffers)
+        return fail(GSR_ERR_INVALID, "null per-view array");
+    if (P > 0 && (!means3D || !opacities || (!cov3D_precomp && (!scales || !rotations))))
+        return fail(GSR_ERR_INVALID, "null parameter array");
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
+    CameraBwdArgs A = {};
+    PreprocessBwdArgs& p = A.a;  // the parameters and flags of preprocess_bwd_shared; no outputs
+    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
+    p.means3D = means3D; p.shs = shs; p.dc = dc; p.opacities = opacities; p.scales = scales;
+    p.rotations = rotations; p.scale_modifier = scale_modifier; p.cov3D_precomp = cov3D_precomp;
+    p.antialiasing = antialiasing; p.has_invdepth = has_invdepth; p.W = width; p.H = height;
+    A.V = V;
+    for (int v = 0; v < V; v++) {
+        if (R[v] < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
+        if (!viewmatrices[v] || !projmatrices[v] || !campos[v]) return fail(GSR_ERR_INVALID, "null camera");
+        if (P > 0 && (!geom_buffers[v] || (R[v] > 0 && !binning_buffers[v])))
+            return fail(GSR_ERR_ALLOC, "null state buffer");
+        const Camera cam = {viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v], tan_fovy[v]};
+        const ViewState vs = {geom_buffers[v], nullptr, binning_buffers[v], 0, nullptr, nullptr, nullptr};
+        if (P > 0) A.v[v] = bwd_view(sc, cam, vs, R[v], nullptr, nullptr);
+    }
+    A.partial = reinterpret_cast<float*>(workspace);
+    A.dL_dview = dL_dviewmatrix; A.dL_dproj = dL_dprojmatrix; A.dL_dcampos = dL_dcampos;
+    hipStream_t s = (hipStream_t)stream;
+    {
+        ProfScope ps_(PK_CAMERA_BWD, s);
+        HIP_TRY(launch_camera_bwd_views(A, s));
     }
     DEBUG_SYNC(s);
     return GSR_OK;

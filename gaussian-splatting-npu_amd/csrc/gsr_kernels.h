@@ -153,6 +153,25 @@ struct PreprocessBwdViewsArgs {
     BwdView v[MAX_VIEWS];
 };
 
+// Camera gradient of V views (gsr_backward_camera_views; preprocess_bwd.hip): `a` carries the
+// parameters and flags (its outputs are not used), v[] what preprocess_bwd reads per view.
+constexpr int CAM_SUMS = 27;               // 12 dL/dview + 12 dL/dproj + 3 dL/dcampos
+constexpr int CAM_ROW = 32;                // floats per workgroup row of the workspace
+constexpr int CAM_WG_GAUSSIANS = 256;      // Gaussians per workgroup: one per lane
+struct CameraBwdArgs {
+    PreprocessBwdArgs a;
+    int V;
+    BwdView v[MAX_VIEWS];
+    float* partial;  // workspace: [V][nwg][CAM_ROW]
+    int nwg;         // set by the launcher: camera_bwd_workgroups(a.P)
+    float* dL_dview;    // (V,4,4)
+    float* dL_dproj;    // (V,4,4)
+    float* dL_dcampos;  // (V,3)
+};
+int camera_bwd_workgroups(int P);
+size_t camera_bwd_workspace_bytes(int V, int P);
+hipError_t launch_camera_bwd_views(const CameraBwdArgs& a, hipStream_t s);
+
 struct AdamArgs {
     float* param;
     const float* grad;

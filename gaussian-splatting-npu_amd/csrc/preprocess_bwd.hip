@@ -220,6 +220,16 @@ struct ViewGrad {
     float dRGB[3];
 };
 
+// Where view_grad<true> adds a (Gaussian, view)'s share of the camera gradient
+// (camera_bwd_views_kernel): the lane's 24 running sums of dL/dviewmatrix (sum 3 r + c: row r,
+// column c < 3) and dL/dprojmatrix (12 + 3 r + c: columns 0, 1, 3), CAM_ACC_STRIDE floats apart.
+// Each share is added where its factors are formed, so none of them stays live behind it.
+constexpr int CAM_ACC_STRIDE = 256;
+struct CamAcc {
+    float* col;
+    __device__ __forceinline__ void add(int q, float x) const { col[q * CAM_ACC_STRIDE] += x; }
+};
+
 // The 3D covariance of a Gaussian: precomputed, or recomputed from scale and rotation
 // (forward.cu:114-151; bit-identical to the forward's).  Always into the local array: a pointer
 // choosing between two arrays would force both into scratch memory.
@@ -241,9 +251,12 @@ __device__ __forceinline__ void cov3d_of(const PreprocessBwdArgs& a, const BwdIn
 // forward does not store -- are recomputed here from the 2D covariance this function recomputes
 // anyway, with the forward's own operations (preprocess.hip preprocess_one, -ffp-contract=off):
 // bit-identical to the stored values.
+// CAM: also add the camera gradient's shares into *ca (CamAcc) -- from the same values the lines
+// above them use; without CAM the parameter is not touched and the code is what it was.
+template <bool CAM = false>
 __device__ __forceinline__ void view_grad(const PreprocessBwdArgs& a, const ViewCam& vc, const float (&gin)[GF_NUM],
                                           uint8_t clamped, const f3 mean, float opacity, const float (&cov3D)[6],
-                                          ViewGrad& o)
+                                          ViewGrad& o, const CamAcc* ca = nullptr)
 {
     float* g = o.g;
 #pragma unroll
@@ -365,6 +378,23 @@ __device__ __forceinline__ void view_grad(const PreprocessBwdArgs& a, const View
     float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 +
                    (2 * h_y * t.y) * tz3 * dL_dJ12;
     if (a.has_invdepth) dL_dtz -= g[GF_INVDEPTH] / (t.z * t.z);
+    if constexpr (CAM) {
+        // dL/dV[k][c] += sum_a dL/dT[a][k] J[a][c] (T = J V[:3,:3]^T: the rotation block in cov2D;
+        // J.m[a] is row a of the 2x3 Jacobian, with the clamped tx, ty), then += mh[r] dL/dt[c]
+        const float dT0[3] = {dL_dT00, dL_dT01, dL_dT02}, dT1[3] = {dL_dT10, dL_dT11, dL_dT12};
+        const float dt[3] = {dL_dtx, dL_dty, dL_dtz};
+        const float mh[4] = {mean.x, mean.y, mean.z, 1.f};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            ca->add(3 * k, dT0[k] * J.m[0][0]);
+            ca->add(3 * k + 1, dT1[k] * J.m[1][1]);
+            ca->add(3 * k + 2, dT0[k] * J.m[0][2] + dT1[k] * J.m[1][2]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) ca->add(3 * r + c, mh[r] * dt[c]);
+    }
     const f3 dm_cov = transformVec4x3Transpose({dL_dtx, dL_dty, dL_dtz}, view);
     float dmx = dm_cov.x, dmy = dm_cov.y, dmz = dm_cov.z;
 
@@ -380,6 +410,15 @@ __device__ __forceinline__ void view_grad(const PreprocessBwdArgs& a, const View
         dmx += (proj[0] * m_w - proj[3] * mul1) * g2x + (proj[1] * m_w - proj[3] * mul2) * g2y;
         dmy += (proj[4] * m_w - proj[7] * mul1) * g2x + (proj[5] * m_w - proj[7] * mul2) * g2y;
         dmz += (proj[8] * m_w - proj[11] * mul1) * g2x + (proj[9] * m_w - proj[11] * mul2) * g2y;
+        if constexpr (CAM) {
+            // dL/dPm[r][c] += mh[r] dL/dp_hom[c], p_hom = [m,1] Pm (column 2 takes no part)
+            const float dph[3] = {m_w * g2x, m_w * g2y, -(mul1 * g2x + mul2 * g2y)};
+            const float mh[4] = {m.x, m.y, m.z, 1.f};
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) ca->add(12 + 3 * r + c, mh[r] * dph[c]);
+        }
     }
     o.dmx = dmx;
     o.dmy = dmy;
@@ -538,20 +577,24 @@ __device__ __forceinline__ void view_load(const PreprocessBwdViewsArgs& A, int i
 #define GSR_CAM_STRIDE 41
 #endif
 constexpr int CAM_FLOATS = GSR_CAM_STRIDE;
+// field j of a camera's LDS row
+__device__ __forceinline__ float cam_field(const BwdView& bv, int j)
+{
+    float x = 0.f;
+    if (j < 16) x = bv.view[j];
+    else if (j < 32) x = bv.proj[j - 16];
+    else if (j < 35) x = bv.campos[j - 32];
+    else if (j == 35) x = bv.focal_x;
+    else if (j == 36) x = bv.focal_y;
+    else if (j == 37) x = bv.tan_fovx;
+    else if (j == 38) x = bv.tan_fovy;
+    return x;
+}
 __device__ __forceinline__ void cams_to_lds(const PreprocessBwdViewsArgs& A, float (*s_cam)[CAM_FLOATS])
 {
     for (int t = threadIdx.x; t < A.V * CAM_FLOATS; t += blockDim.x) {
         const int v = t / CAM_FLOATS, j = t - v * CAM_FLOATS;
-        const BwdView& bv = A.v[v];
-        float x = 0.f;
-        if (j < 16) x = bv.view[j];
-        else if (j < 32) x = bv.proj[j - 16];
-        else if (j < 35) x = bv.campos[j - 32];
-        else if (j == 35) x = bv.focal_x;
-        else if (j == 36) x = bv.focal_y;
-        else if (j == 37) x = bv.tan_fovx;
-        else if (j == 38) x = bv.tan_fovy;
-        s_cam[v][j] = x;
+        s_cam[v][j] = cam_field(A.v[v], j);
     }
 }
 
@@ -930,6 +973,191 @@ hipError_t launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& A, hipStrea
     if (A.V <= 4) return launch_views<4>(A, s);
     if (A.V <= 8) return launch_views<8>(A, s);
     return launch_views<16>(A, s);
+}
+
+// ---- camera gradient (gsr_backward_camera_views) -------------------------------------------
+// dL/dviewmatrix, dL/dprojmatrix and dL/dcampos of every view of a batch: the other side of the
+// products view_grad keeps for dL/dmean3D, summed over the view's visible Gaussians.  With V the
+// view matrix as stored (t = [m,1] V), Pm the full projection (p_hom = [m,1] Pm), mh = (m, 1):
+//   dL/dV[r][c]  += mh[r] dL/dt[c]                        (r 0..3, c 0..2)
+//   dL/dV[k][c]  += sum_a dL/dT[a][k] J[a][c]             (k, c 0..2: the rotation block of cov2D)
+//   dL/dPm[r][c] += mh[r] dL/dp_hom[c],  dL/dp_hom = (m_w g2x, m_w g2y, 0, -(mul1 g2x + mul2 g2y))
+//   dL/dcampos   -= the view-direction (SH) term of dL/dmean3D
+// 27 sums per view (column 3 of dL/dV and column 2 of dL/dPm are zero).  One workgroup per (block of
+// CAM_WG_GAUSSIANS = 256 Gaussians, view), the view varying fastest, one Gaussian per lane: the wave's lanes are summed in
+// one xor butterfly, the four waves in order through LDS -- one CAM_ROW-float row per workgroup in
+// the workspace, which camera_bwd_finish_kernel sums per view in a fixed order.  No atomics; the
+// launch shape depends on P alone, so a view's sums are the same bits alone or in a batch.
+// (Several Gaussians per lane in a loop, fewer rows, cost 154 VGPRs against 84: the loop stays out.)
+// Reads, per visible (Gaussian, view), what preprocess_bwd reads (parameters ~44-68 B, the 13-B
+// view state, its flagged 40-B records, its SH row) and writes 128 B per workgroup.
+static_assert(CAM_WG_GAUSSIANS == 256, "one Gaussian per lane of a 256-thread workgroup");
+
+__global__ void __launch_bounds__(256) camera_bwd_views_kernel(const CameraBwdArgs A)
+{
+    const PreprocessBwdArgs& a = A.a;
+    // the V workgroups of one block of Gaussians are neighbours in the grid: the parameters and SH
+    // rows the first one reads are in L2 for the others
+    const int v = (int)(blockIdx.x % (unsigned)A.V), wg = (int)(blockIdx.x / (unsigned)A.V), tid = (int)threadIdx.x;
+    const BwdView& bv = A.v[v];
+    __shared__ float s_cam[CAM_FLOATS];
+    __shared__ float s_red[4][CAM_ROW];
+    // the lane's 27 sums: its own LDS column (bank = lane: conflict-free), so that none of them is
+    // a live register across view_grad
+    __shared__ float s_acc[CAM_SUMS][CAM_ACC_STRIDE];
+    if (tid < CAM_FLOATS) s_cam[tid] = cam_field(bv, tid);
+#pragma unroll
+    for (int q = 0; q < CAM_SUMS; q++) s_acc[q][tid] = 0.f;
+    __syncthreads();
+    const ViewCam vc = cam_of_lds(s_cam);
+    const int nc = sh_ncoef(a);
+    const int idx = wg * CAM_WG_GAUSSIANS + tid;
+    // visible <=> a tile count > 0 (view_visible_in)
+    const uint32_t n = idx < a.P ? bv.tiles_touched[idx] : 0u;
+    if (n > 0) {
+        const size_t i = (size_t)idx;
+        BwdIn in;
+        bwd_gather(a, idx, in);
+        float gs[GF_NUM];
+        gather_any<REC_BATCH>(bv.emit_start[idx], n, bv.rec_mask[idx], bv.valid, bv.grad_inst, gs);
+        float cov3D[6];
+        cov3d_of(a, in, cov3D);
+        ViewGrad o;
+        const CamAcc ca = {&s_acc[0][tid]};
+        view_grad<true>(a, vc, gs, bv.clamped[idx], in.mean, in.opacity, cov3D, o, &ca);
+        if (nc > 1) {  // degree 0 has no direction dependence
+            const float* c0 = a.dc ? a.dc + 3 * i : a.shs + i * (size_t)a.M * 3;
+            const float* cr = a.dc ? a.shs + i * (size_t)(a.M - 1) * 3 : c0 + 3;
+            // interleaved 48-float rows: 16-byte loads (a lane's row is its own 192 B: a 4-byte load
+            // per lane touches 64 lines per instruction, a 16-byte one a quarter as often)
+            const bool vec = !a.dc && a.M == 16 && ((uintptr_t)a.shs % 16) == 0;
+            float ddir[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < 4; kb++) {  // four coefficients (12 floats) at a time, in order
+                if (4 * kb < nc) {
+                    float q[12];
+                    if (vec) {
+                        const float4* r4 = reinterpret_cast<const float4*>(c0) + 3 * kb;
+#pragma unroll
+                        for (int u = 0; u < 3; u++) {
+                            const float4 x = r4[u];
+                            q[4 * u] = x.x; q[4 * u + 1] = x.y; q[4 * u + 2] = x.z; q[4 * u + 3] = x.w;
+                        }
+                    } else {
+#pragma unroll
+                        for (int kk = 0; kk < 4; kk++) {
+                            const int k = 4 * kb + kk;
+                            const float* shk = k == 0 ? c0 : cr + 3 * (k - 1);
+#pragma unroll
+                            for (int c = 0; c < 3; c++) q[3 * kk + c] = k < nc ? shk[c] : 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < 4; kk++) {
+                        const int k = 4 * kb + kk;
+                        if (k < nc) {
+                            float b, gx, gy, gz;
+                            sh_term(k, o.x, o.y, o.z, b, gx, gy, gz);
+#pragma unroll
+                            for (int c = 0; c < 3; c++) {
+                                const float t = q[3 * kk + c] * o.dRGB[c];
+                                ddir[0] += t * gx;
+                                ddir[1] += t * gy;
+                                ddir[2] += t * gz;
+                            }
+                        }
+                    }
+                }
+            }
+            const f3 dn = dnormvdv(o.dir_orig, {ddir[0], ddir[1], ddir[2]});
+            s_acc[24][tid] -= dn.x;
+            s_acc[25][tid] -= dn.y;
+            s_acc[26][tid] -= dn.z;
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int q = 0; q < CAM_SUMS; q++) {
+        float x = s_acc[q][tid];
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) x += __shfl_xor(x, off, 64);
+        if (lane == 0) s_red[wave][q] = x;
+    }
+    __syncthreads();
+    if (tid < CAM_SUMS) {
+        const float x = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
+        A.partial[((size_t)v * A.nwg + wg) * CAM_ROW + tid] = x;
+    }
+}
+
+// One workgroup per view: the view's workgroup rows in CAM_STRANDS strands (rows s, s + CAM_STRANDS,
+// ... in order, eight loads in flight), the strands in order; then the three outputs, structural
+// zeros included.
+constexpr int CAM_STRANDS = 32;
+__global__ void __launch_bounds__(32 * CAM_STRANDS) camera_bwd_finish_kernel(const float* partial, int nwg,
+                                                                             float* dL_dview, float* dL_dproj,
+                                                                             float* dL_dcampos)
+{
+    __shared__ float s_part[CAM_STRANDS][CAM_ROW];
+    __shared__ float s_tot[CAM_ROW];
+    const int v = (int)blockIdx.x, q = (int)threadIdx.x & 31, strand = (int)threadIdx.x >> 5;
+    float x = 0.f;
+    if (q < CAM_SUMS) {
+        for (int r0 = strand; r0 < nwg; r0 += 8 * CAM_STRANDS) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int r = r0 + u * CAM_STRANDS;
+                t[u] = r < nwg ? partial[((size_t)v * nwg + r) * CAM_ROW + q] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) x += t[u];
+        }
+    }
+    s_part[strand][q] = x;
+    __syncthreads();
+    if (threadIdx.x < CAM_ROW) {
+        float t = s_part[0][q];
+#pragma unroll
+        for (int k = 1; k < CAM_STRANDS; k++) t += s_part[k][q];
+        s_tot[q] = t;
+    }
+    __syncthreads();
+    const int t = (int)threadIdx.x;
+    if (t < 16) {
+        const int r = t >> 2, c = t & 3;
+        dL_dview[v * 16 + t] = c < 3 ? s_tot[3 * r + c] : 0.f;
+    } else if (t < 32) {
+        const int r = (t - 16) >> 2, c = t & 3;  // columns 0, 1, 3 hold sums 0, 1, 2
+        dL_dproj[v * 16 + t - 16] = c == 2 ? 0.f : s_tot[12 + 3 * r + (c == 3 ? 2 : c)];
+    } else if (t < 35) {
+        dL_dcampos[v * 3 + t - 32] = s_tot[24 + t - 32];
+    }
+}
+
+int camera_bwd_workgroups(int P) { return P > 0 ? (P + CAM_WG_GAUSSIANS - 1) / CAM_WG_GAUSSIANS : 0; }
+
+size_t camera_bwd_workspace_bytes(int V, int P)
+{
+    const size_t rows = (size_t)(V > 0 ? V : 0) * (size_t)camera_bwd_workgroups(P);
+    return (rows > 0 ? rows : 1) * CAM_ROW * sizeof(float);
+}
+
+hipError_t launch_camera_bwd_views(const CameraBwdArgs& A_, hipStream_t s)
+{
+    if (A_.V < 1 || A_.V > MAX_VIEWS || A_.a.P < 0) return hipErrorInvalidValue;
+    if (!A_.partial || !A_.dL_dview || !A_.dL_dproj || !A_.dL_dcampos) return hipErrorInvalidValue;
+    CameraBwdArgs A = A_;
+    A.a.acc = 0;
+    A.nwg = camera_bwd_workgroups(A.a.P);
+    if (A.nwg > 0) {
+        hipLaunchKernelGGL(camera_bwd_views_kernel, dim3((unsigned)A.nwg * (unsigned)A.V), dim3(256), 0, s, A);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(camera_bwd_finish_kernel, dim3(A.V), dim3(32 * CAM_STRANDS), 0, s, A.partial, A.nwg, A.dL_dview,
+                       A.dL_dproj, A.dL_dcampos);
+    return hipGetLastError();
 }
 
 }  // namespace gsr

@@ -59,6 +59,10 @@ def _load(path=LIB_PATH):
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _b, _b, ctypes.c_uint, _vp]
     lib.gsr_backward_preprocess_views_range.argtypes = lib.gsr_backward_preprocess_views.argtypes[:-1] + [_i, _i, _vp]
     lib.gsr_backward_render_views.argtypes = [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _b, _vp]
+    lib.gsr_camera_grad_workspace_size.restype = _sz
+    lib.gsr_camera_grad_workspace_size.argtypes = [_i, _i]
+    lib.gsr_backward_camera_views.argtypes = [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _b, _b, _vp, _vp, _vp, _vp, _b, _vp]
     lib.gsr_forward_views.argtypes = [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _b, _b, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _b, _vp, _vp,
                                       _vp]
@@ -623,6 +627,81 @@ def rasterize_gaussians_preprocess_backward_views(means3D, radii, colors, opacit
         r["sh"].data_ptr() if M else None, r["scales"].data_ptr(), r["rotations"].data_ptr(), bool(antialiasing),
         bool(debug), mask, _stream(dev)))
     return _views_result(dL_dmeans2D, r, acc, has_dc)
+
+
+def _camera_check(name, t, shape):
+    """One camera array (or camera gradient) of backward_camera_views: float32, contiguous, `shape`."""
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name} must have shape {shape}, got {got}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous, got strides {tuple(t.stride())}")
+
+
+def camera_grad_workspace_size(V, P):
+    """Bytes of gsr_backward_camera_views' workspace for V views of P Gaussians."""
+    return int(lib.gsr_camera_grad_workspace_size(int(V), int(P)))
+
+
+def backward_camera_views(means3D, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                          projmatrices, campos, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
+                          geomBuffers, Rs, binningBuffers, has_invdepth, antialiasing, debug, dc=None,
+                          dL_dviewmatrices=None, dL_dprojmatrices=None, dL_dcampos=None):
+    """gsr_backward_camera_views: the camera gradient of V views whose render backward already ran
+    (before or after their preprocess backward; the state is only read).  viewmatrices and
+    projmatrices (V,4,4) and campos (V,3): contiguous float32, stacked as the forward took them
+    (row-major as torch stores them); the per-view lists (tan_fovx, tan_fovy, geomBuffers, Rs,
+    binningBuffers) and the Gaussians as rasterize_gaussians_preprocess_backward_views takes them.
+    Returns (dL_dviewmatrices (V,4,4), dL_dprojmatrices (V,4,4), dL_dcampos (V,3)): fresh tensors, or
+    the given ones (contiguous float32 of those shapes), fully written; column 3 of dL/dview and
+    column 2 of dL/dproj are zero.  Bitwise reproducible; a view's gradient is the same bits alone or
+    in a batch."""
+    if not isinstance(viewmatrices, torch.Tensor) or viewmatrices.dim() != 3:
+        got = tuple(viewmatrices.shape) if isinstance(viewmatrices, torch.Tensor) else type(viewmatrices).__name__
+        raise RuntimeError(f"viewmatrices must have shape (views, 4, 4), got {got}")
+    V = viewmatrices.size(0)
+    cams = (("viewmatrices", viewmatrices, (V, 4, 4)), ("projmatrices", projmatrices, (V, 4, 4)),
+            ("campos", campos, (V, 3)))
+    outs = (("dL_dviewmatrices", dL_dviewmatrices, (V, 4, 4)), ("dL_dprojmatrices", dL_dprojmatrices, (V, 4, 4)),
+            ("dL_dcampos", dL_dcampos, (V, 3)))
+    for name, t, shape in cams:
+        _camera_check(name, t, shape)
+    for name, t, shape in outs:
+        if t is not None:
+            _camera_check(name, t, shape)
+    if not 1 <= V <= 16:
+        raise RuntimeError(f"viewmatrices: 1 to 16 views, got {V}")
+    for name, seq in (("tan_fovx", tan_fovx), ("tan_fovy", tan_fovy), ("geomBuffers", geomBuffers), ("Rs", Rs),
+                      ("binningBuffers", binningBuffers)):
+        if len(seq) != V:
+            raise RuntimeError(f"{name} must have one entry per view ({V}), got {len(seq)}")
+    dev = _act_device([(name, t) for name, t, _ in cams + outs if t is not None])
+    _require_gpu(means3D)
+    P = means3D.size(0)
+    M, has_dc = _sh_split(sh, dc)
+    grads = [t if t is not None else torch.empty(shape, dtype=torch.float32, device=dev) for _, t, shape in outs]
+    keep = []
+
+    def p(t, name):
+        ptr, tt = _ptr(t, name, dev)
+        keep.append(tt)
+        return ptr
+
+    workspace = torch.empty((camera_grad_workspace_size(V, P),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.gsr_backward_camera_views(
+            V, P, int(degree), M, (_i * V)(*[int(x) for x in Rs]), int(image_width), int(image_height),
+            p(means3D, "means3D"), p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"),
+            p(opacities, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
+            p(cov3D_precomp, "cov3D_precomp"), _ptr_array([viewmatrices[v] for v in range(V)]),
+            _ptr_array([projmatrices[v] for v in range(V)]), _ptr_array([campos[v] for v in range(V)]),
+            (_f * V)(*[float(x) for x in tan_fovx]), (_f * V)(*[float(x) for x in tan_fovy]),
+            _ptr_array(geomBuffers), _ptr_array([b if b.numel() else None for b in binningBuffers]),
+            bool(has_invdepth), bool(antialiasing), workspace.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
+            grads[2].data_ptr(), bool(debug), _stream(dev)))
+    return tuple(grads)
 
 
 def _adam_check(param, param_grad, exp_avg, exp_avg_sq, N, M, dev):

@@ -22,7 +22,7 @@ from . import _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "SparseGaussianAdam",
            "accumulate_grads_in_place", "deferred_backward", "MultiViewRasterizer", "rasterize_views",
-           "grad_chunk_hook", "fused_activations"]
+           "grad_chunk_hook", "fused_activations", "rasterize_gaussians_camera", "rasterize_views_camera"]
 
 _state = threading.local()
 
@@ -378,6 +378,68 @@ class _RasterizeGaussians(torch.autograd.Function):
                 grad_rotations, grad_cov3Ds_precomp, None, grad_dc, None)
 
 
+def _camera_guard(keyword):
+    """camera= / cameras= take no part in a deferred or chunk-hooked backward: those run the
+    per-Gaussian half later or in ranges, and hand out parameter gradients only."""
+    if getattr(_state, "deferred", None) is not None:
+        raise RuntimeError(f"{keyword} cannot be combined with deferred_backward(): the camera gradient is "
+                           "computed in the view's own backward")
+    if _grad_chunks is not None:
+        raise RuntimeError(f"{keyword} cannot be combined with grad_chunk_hook: the chunked backward hands out "
+                           "parameter gradients only")
+
+
+def _camera_triple(keyword, viewmatrix, projmatrix, campos, lead=()):
+    """The three camera tensors of camera= (lead = ()) or cameras= (lead = (V,)), checked."""
+    for name, t, shape in (("viewmatrix", viewmatrix, lead + (4, 4)), ("projmatrix", projmatrix, lead + (4, 4)),
+                           ("campos", campos, lead + (3,))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise RuntimeError(f"{keyword}: {name} must be a float32 tensor of shape {shape}")
+
+
+def rasterize_gaussians_camera(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                               raster_settings, dc, viewmatrix, projmatrix, campos):
+    """rasterize_gaussians with the settings' camera replaced by three tensors that take part in
+    autograd (GaussianRasterizer.forward's camera=)."""
+    _camera_guard("camera=")
+    _camera_triple("camera=", viewmatrix, projmatrix, campos)
+    return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                           cov3Ds_precomp, raster_settings, dc, viewmatrix, projmatrix, campos)
+
+
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """_RasterizeGaussians with dL/dviewmatrix (4,4), dL/dprojmatrix (4,4) and dL/dcampos (3,):
+    the existing forward on the detached camera values, the existing backward, then one
+    _C.backward_camera_views call over the same state (gsr_backward_camera_views).  Everything the
+    existing node returns is what it returns without camera=, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, dc, viewmatrix, projmatrix, campos):
+        cam = tuple(t.detach().contiguous() for t in (viewmatrix, projmatrix, campos))
+        s = raster_settings._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2])
+        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                           cov3Ds_precomp, s, dc)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_out_depth):
+        _camera_guard("camera=")
+        grads = _RasterizeGaussians.backward(ctx, grad_out_color, grad_radii, grad_out_depth)[:10]
+        if not any(ctx.needs_input_grad[10:13]):
+            return grads + (None, None, None)
+        s = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, _radii, sh, opacities, geomBuffer,
+         binningBuffer, _imgBuffer, dc) = ctx.saved_tensors
+        has_inv = grad_out_depth is not None and grad_out_depth.numel() != 0
+        g_view, g_proj, g_campos = _C.backward_camera_views(
+            means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+            s.viewmatrix.unsqueeze(0), s.projmatrix.unsqueeze(0), s.campos.unsqueeze(0), [s.tanfovx], [s.tanfovy],
+            s.image_height, s.image_width, sh, s.sh_degree, [geomBuffer], [ctx.num_rendered], [binningBuffer],
+            has_inv, s.antialiasing, s.debug, dc=dc)
+        cam = (g_view[0], g_proj[0], g_campos[0])
+        return grads + tuple(g if need else None for g, need in zip(cam, ctx.needs_input_grad[10:13]))
+
+
 def fused_activations(scaling, rotation, opacity):
     """(scales, rotations, opacities) = (exp(scaling), normalize(rotation), sigmoid(opacity)):
     GaussianModel.get_scaling / get_rotation / get_opacity (gaussian_model.py:102-135) as ONE HIP
@@ -450,9 +512,13 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None):
+                cov3D_precomp=None, dc=None, camera=None):
         """``dc`` (P,1,3), keyword only in practice (gaussian_renderer/__init__.py:91-100): SH
-        coefficient 0, with ``shs`` then holding coefficients 1.. (features_rest)."""
+        coefficient 0, with ``shs`` then holding coefficients 1.. (features_rest).
+        ``camera`` = (viewmatrix (4,4), projmatrix (4,4), campos (3,)): float32 tensors on the device
+        that replace the settings' three for this call and take part in autograd (pose refinement:
+        multiview.pose_camera); those that require grad receive dL/dviewmatrix, dL/dprojmatrix and
+        dL/dcampos, everything else is what the call without ``camera`` gives."""
         s = self.raster_settings
         if (shs is None) == (colors_precomp is None) or (dc is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -460,6 +526,17 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         absent = torch.Tensor([])
+        if camera is not None:
+            viewmatrix, projmatrix, campos = camera
+            return rasterize_gaussians_camera(
+                means3D, means2D,
+                absent if shs is None else shs,
+                absent if colors_precomp is None else colors_precomp,
+                opacities,
+                absent if scales is None else scales,
+                absent if rotations is None else rotations,
+                absent if cov3D_precomp is None else cov3D_precomp,
+                s, dc, viewmatrix, projmatrix, campos)
         return rasterize_gaussians(
             means3D, means2D,
             absent if shs is None else shs,
@@ -584,6 +661,48 @@ class _RasterizeViews(torch.autograd.Function):
                 grad_rotations, grad_cov3Ds_precomp, None, grad_dc)
 
 
+def rasterize_views_camera(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                           raster_settings, dc, viewmatrices, projmatrices, campos):
+    """rasterize_views with the views' cameras replaced by stacked tensors (V,4,4), (V,4,4), (V,3)
+    that take part in autograd (MultiViewRasterizer.forward's cameras=)."""
+    _camera_guard("cameras=")
+    _camera_triple("cameras=", viewmatrices, projmatrices, campos, lead=(len(raster_settings),))
+    return _RasterizeViewsCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                       cov3Ds_precomp, tuple(raster_settings), dc, viewmatrices, projmatrices, campos)
+
+
+class _RasterizeViewsCamera(torch.autograd.Function):
+    """_RasterizeViews with the stacked dL/dviewmatrices (V,4,4), dL/dprojmatrices (V,4,4) and
+    dL/dcampos (V,3): the existing batched forward and backward, then one
+    _C.backward_camera_views call for the batch (see _RasterizeGaussiansCamera)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                raster_settings, dc, viewmatrices, projmatrices, campos):
+        ctx.cameras = tuple(t.detach().contiguous() for t in (viewmatrices, projmatrices, campos))
+        ss = tuple(s._replace(viewmatrix=ctx.cameras[0][v], projmatrix=ctx.cameras[1][v], campos=ctx.cameras[2][v])
+                   for v, s in enumerate(raster_settings))
+        return _RasterizeViews.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                       cov3Ds_precomp, ss, dc)
+
+    @staticmethod
+    def backward(ctx, grad_colors, grad_radii, grad_invdepths):
+        _camera_guard("cameras=")
+        grads = _RasterizeViews.backward(ctx, grad_colors, grad_radii, grad_invdepths)
+        if not any(ctx.needs_input_grad[10:13]):
+            return grads + (None, None, None)
+        ss = ctx.raster_settings
+        s0 = ss[0]
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, _radii, sh, opacities, dc,
+         *bufs) = ctx.saved_tensors
+        has_inv = grad_invdepths is not None and grad_invdepths.numel() != 0
+        cam = _C.backward_camera_views(
+            means3D, colors_precomp, opacities, scales, rotations, s0.scale_modifier, cov3Ds_precomp, *ctx.cameras,
+            [s.tanfovx for s in ss], [s.tanfovy for s in ss], s0.image_height, s0.image_width, sh, s0.sh_degree,
+            bufs[0::3], ctx.num_rendered, bufs[1::3], has_inv, s0.antialiasing, s0.debug, dc=dc)
+        return grads + tuple(g if need else None for g, need in zip(cam, ctx.needs_input_grad[10:13]))
+
+
 class MultiViewRasterizer(nn.Module):
     """GaussianRasterizer over a batch of V <= 16 views of the same Gaussians (one settings tuple
     per view; image size, background, scale modifier, SH degree and flags shared).  forward takes
@@ -607,9 +726,29 @@ class MultiViewRasterizer(nn.Module):
         self.raster_settings = ss
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None):
+                cov3D_precomp=None, dc=None, cameras=None):
+        """``cameras``: the views' cameras as stacked float32 tensors (viewmatrices (V,4,4),
+        projmatrices (V,4,4), campos (V,3)) or a list of V (viewmatrix, projmatrix, campos) triples;
+        they replace the settings' for this call and take part in autograd
+        (GaussianRasterizer.forward's ``camera``, per view)."""
         _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
         absent = torch.Tensor([])
+        if cameras is not None:
+            if len(cameras) == 3 and all(isinstance(t, torch.Tensor) and t.dim() >= 2 for t in cameras):
+                viewmatrices, projmatrices, campos = cameras
+            else:
+                if len(cameras) != len(self.raster_settings):
+                    raise RuntimeError(f"cameras=: {len(self.raster_settings)} views, got {len(cameras)} cameras")
+                viewmatrices, projmatrices, campos = (torch.stack([c[k] for c in cameras]) for k in range(3))
+            return rasterize_views_camera(
+                means3D, means2D,
+                absent if shs is None else shs,
+                absent if colors_precomp is None else colors_precomp,
+                opacities,
+                absent if scales is None else scales,
+                absent if rotations is None else rotations,
+                absent if cov3D_precomp is None else cov3D_precomp,
+                self.raster_settings, dc, viewmatrices, projmatrices, campos)
         return rasterize_views(
             means3D, means2D,
             absent if shs is None else shs,

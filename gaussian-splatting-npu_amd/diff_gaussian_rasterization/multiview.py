@@ -388,6 +388,32 @@ def view_from_camera(cam, bg, sh_degree=3, scale_modifier=1.0, debug=False, anti
     return settings, cam.original_image.to(dev), extras
 
 
+def pose_camera(cam, delta):
+    """A camera moved by a learnable pose delta, for GaussianRasterizer.forward's ``camera=`` /
+    MultiViewRasterizer.forward's ``cameras=``.  cam: a base camera as view_from_camera takes it
+    (world_view_transform and projection_matrix, (4,4) as the reference stores them: row vectors,
+    p_view = [p,1] @ view); delta: 6 values, an axis-angle rotation w = delta[:3] and a translation
+    t = delta[3:], both in the camera frame: p_view' = R(w) p_view + t.  Returns (viewmatrix,
+    full_proj, campos), differentiable in delta and in delta's dtype and device:
+        view = base_view @ exp(delta),  full_proj = view @ projection_matrix,
+        campos = inverse(view)[3, :3]
+    (scene/cameras.py:86-89 for the moved camera); delta = 0 gives the base camera's own three."""
+    if delta.shape != (6,):
+        raise RuntimeError(f"delta must have shape (6,), got {tuple(delta.shape)}")
+    base = cam.world_view_transform.to(delta)
+    proj = cam.projection_matrix.to(delta)
+    w, t = delta[:3], delta[3:]
+    zero = torch.zeros((), dtype=delta.dtype, device=delta.device)
+    skew = torch.stack([torch.stack([zero, -w[2], w[1]]), torch.stack([w[2], zero, -w[0]]),
+                        torch.stack([-w[1], w[0], zero])])
+    R = torch.linalg.matrix_exp(skew)  # Rodrigues' rotation, differentiable at w = 0
+    last = torch.tensor([[0.0], [0.0], [0.0], [1.0]], dtype=delta.dtype, device=delta.device)
+    # row-vector form of p -> R p + t: [[R^T, 0], [t, 1]]
+    E = torch.cat([torch.cat([R.transpose(0, 1), t[None]], 0), last], 1)
+    view = base @ E
+    return view, view @ proj, torch.linalg.inv(view)[3, :3]
+
+
 def views_from_cameras(cameras, bg, sh_degree=3, **kw):
     """view_from_camera over a Scene's train cameras (scene.getTrainCameras()), the camera's index
     in the list as its exposure index (train.py's `vind`, gaussian_model.py:175-176)."""

@@ -328,6 +328,43 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
                                         bool antialiasing, bool debug, unsigned accumulate, int g_begin, int g_end,
                                         gsr_stream_t stream);
 
+/* The camera gradient of V <= 16 views: dL/dviewmatrix, dL/dprojmatrix and dL/dcampos of each view,
+ * which no other entry point returns (the reference treats the camera as a constant).  Called after
+ * the views' render backward (gsr_backward*, gsr_backward_render or gsr_backward_render_views), before
+ * or after their preprocess backward, and before the next forward into the same state buffers; it
+ * only reads the state (the gradient records stay valid until then).  Arguments as
+ * gsr_backward_preprocess_views; a Gaussian counts for a view iff the forward gave it tiles there
+ * (the forward state, not a caller's radii).
+ * With V = viewmatrix and Pm = projmatrix as stored, row-major (4,4) as torch stores them
+ * (t = [m,1] V the view-space mean, p_hom = [m,1] Pm), mh = (m.x, m.y, m.z, 1), and the factors
+ * BACKWARD::preprocess forms per visible Gaussian (backward.cu:147-326, 423-440):
+ *   dL/dV[r][c]  = sum_i mh[r] dL/dt[c]                                   r 0..3, c 0..2
+ *                + sum_i sum_a dL/dT[a][r] J[a][c]                        r, c 0..2
+ *     dL/dt: the reference's dL_dtx, dL_dty, dL_dtz (clamp multipliers and inverse-depth term
+ *     included); T = J V[:3,:3]^T the 2x3 factor of cov2D = T cov3D T^T with dL/dT the reference's
+ *     dL_dT00 .. dL_dT12; J = [[fx/tz, 0, -fx tx/tz^2], [0, fy/tz, -fy ty/tz^2]] with the clamped tx, ty;
+ *   dL/dPm[r][c] = sum_i mh[r] dL/dp_hom[c],
+ *     dL/dp_hom = (m_w g2x, m_w g2y, 0, -(mul1 g2x + mul2 g2y)), g2 = dL/dmean2D, m_w = 1/(p_hom.w + 1e-7),
+ *     mul1 = p_hom.x m_w^2, mul2 = p_hom.y m_w^2;
+ *   dL/dcampos   = -sum_i (the view-direction term of dL/dmean3D: computeColorFromSH's backward,
+ *     backward.cu:103-141); zero with colors_precomp or degree 0.
+ * Column 3 of dL/dV and column 2 of dL/dPm are written as zeros.  The three outputs (device memory:
+ * V*16, V*16 and V*3 floats) are fully written, also for P == 0 (zeros).  workspace:
+ * gsr_camera_grad_workspace_size(V, P) bytes of device memory, 4-byte aligned, contents irrelevant on
+ * entry (monotone in V and P).  No atomics: the sums are bitwise reproducible, and a view's are the
+ * same bits alone or inside a batch.  V outside [1, 16], P < 0, a NULL output, workspace or per-view
+ * array: GSR_ERR_INVALID.  Asynchronous; never throws (status + gsr_last_error). */
+size_t gsr_camera_grad_workspace_size(int V, int P);
+int gsr_backward_camera_views(int V, int P, int D, int M, const int* R, int width, int height, const float* means3D,
+                              const float* dc, const float* shs, const float* colors_precomp,
+                              const float* opacities, const float* scales, float scale_modifier,
+                              const float* rotations, const float* cov3D_precomp, const float* const* viewmatrices,
+                              const float* const* projmatrices, const float* const* campos, const float* tan_fovx,
+                              const float* tan_fovy, char* const* geom_buffers, char* const* binning_buffers,
+                              bool has_invdepth, bool antialiasing, char* workspace,
+                              float* dL_dviewmatrix /* V*16 */, float* dL_dprojmatrix /* V*16 */,
+                              float* dL_dcampos /* V*3 */, bool debug, gsr_stream_t stream);
+
 /* Forward of a batch of V <= 16 camera views of the same Gaussians (the forward half of
  * gsr_backward_views; each view the result of gsr_forward_prealloc_dc with its own state buffers).
  * Every stage is ONE launch over up to 8 views (grid.y = view), on an internal high-priority

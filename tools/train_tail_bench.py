@@ -46,6 +46,13 @@
           U / P of the scenes the repository has (the trainer test's spread scene, the chair fixture,
           the config-3-scale cloud) and the compact_below the measured copies give with DESIGN.md §8's
           ASSUMED link rate.  Nothing here is timed on more than one GPU.
+  camera: the backward of the bench's step (--views views of --points Gaussians at --width x --height,
+          one MultiViewRasterizer node, the forward re-run untimed before every call) without and with
+          cameras= (the camera gradient: camera_bwd_views_kernel + camera_bwd_finish_kernel), the two
+          alternating call by call; then the kernels' own HIP-event time from the library's profile scopes
+          (gsr_profile_read) over --reps more backward passes with cameras=, beside preprocess_bwd's of the
+          same passes -- the yardstick: the camera kernel reads the same records and visible rows and
+          writes nothing per Gaussian.  Written to the block "camera_grads".
 
 Defaults are the bench's flagship shape: 8 views, 1920x1080, 1M Gaussians, seed-0 data.  The two
 sides alternate call by call; every call is bracketed by device events and ends in a
@@ -66,7 +73,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussian-splatting-npu_amd"))
 
 
-LEGS = ("loss", "view_loss", "stats", "densify", "activations", "iteration", "compact")
+LEGS = ("loss", "view_loss", "stats", "densify", "activations", "iteration", "compact", "camera")
 
 
 def timed(fn, torch):
@@ -157,6 +164,8 @@ def main():
         result["iteration"] = iteration_leg(args, side, torch, fused_l1_ssim_loss, fused_ssim, dev)
     if "compact" in legs:
         result["compact"] = compact_leg(args, torch, multiview, dev)
+    if "camera" in legs:
+        result["camera_grads"] = camera_leg(args, torch, dev)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
@@ -689,6 +698,71 @@ def compact_leg(args, torch, multiview, dev):
     out["compact_below_derivation"] = derived
     out["shipped_compact_below"] = multiview.COMPACT_BELOW
     out["union_fractions"] = unions
+    return out
+
+
+def camera_leg(args, torch, dev):
+    """The batched backward without and with cameras=, and the camera kernels' own time beside
+    preprocess_bwd's (see the module docstring)."""
+    import ctypes
+
+    import diff_gaussian_rasterization as dgr
+    from diff_gaussian_rasterization import _C
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import synthetic
+    V, P, H, W = args.views, args.points, args.height, args.width
+    scene = {k: v.to(dev).requires_grad_(True) for k, v in synthetic.make_scene(P, seed=0).items()}
+    cams = [synthetic.Camera(W, H, view=v, n_views=max(V, 8)) for v in range(V)]
+    bg = torch.zeros(3, device=dev)
+    rast = dgr.MultiViewRasterizer([dgr.GaussianRasterizationSettings(
+        image_height=H, image_width=W, tanfovx=c.tanfovx, tanfovy=c.tanfovy, bg=bg, scale_modifier=1.0,
+        viewmatrix=c.world_view_transform.to(dev), projmatrix=c.full_proj_transform.to(dev), sh_degree=3,
+        campos=c.camera_center.to(dev), prefiltered=False, debug=False, antialiasing=False) for c in cams])
+    stacked = tuple(torch.stack([getattr(c, n) for c in cams]).to(dev).contiguous().requires_grad_(True)
+                    for n in ("world_view_transform", "full_proj_transform", "camera_center"))
+    gc = torch.randn((V, 3, H, W), generator=torch.Generator().manual_seed(1)).to(dev)
+    means2D = torch.zeros((V, P, 3), device=dev, requires_grad=True)
+
+    def prepare(with_cameras):
+        def prep():
+            for t in list(scene.values()) + list(stacked) + [means2D]:
+                t.grad = None
+            color = rast(means3D=scene["means3D"], means2D=means2D, opacities=scene["opacities"], shs=scene["shs"],
+                         scales=scene["scales"], rotations=scene["rotations"],
+                         **({"cameras": stacked} if with_cameras else {}))[0]
+            return lambda: color.backward(gc)
+        return prep
+
+    r = alternate_prepared({"backward": prepare(False), "backward_with_cameras": prepare(True)}, args.warmup,
+                           args.reps, args.rounds, torch)
+    out = {k: {"median_ms": med, "spread_ms": spread, "round_medians_ms": rounds} for k, (med, spread, rounds) in r.items()}
+    out["added_ms"] = r["backward_with_cameras"][0] - r["backward"][0]
+    out["added_beyond_spread"] = bool(out["added_ms"] > max(r["backward"][1], r["backward_with_cameras"][1]))
+    # the kernels' own time: the library's profile scopes around the launches, cameras= passes only
+    lib = _C.lib
+    lib.gsr_profile_kernel_name.restype = ctypes.c_char_p
+    run = prepare(True)
+    run()()  # one pass outside the profile (allocations)
+    torch.cuda.synchronize()
+    lib.gsr_profile_enable(1)
+    for _ in range(args.reps):
+        run()()
+    torch.cuda.synchronize()
+    tot, cnt = (ctypes.c_double * 16)(), (ctypes.c_int * 16)()
+    n = lib.gsr_profile_read(tot, cnt, 16)
+    lib.gsr_profile_enable(0)
+    kern = {lib.gsr_profile_kernel_name(k).decode(): {"avg_ms": tot[k] / cnt[k], "launches": cnt[k]}
+            for k in range(n) if cnt[k]}
+    out["kernels_ms_per_batch"] = {k: kern[k] for k in ("camera_bwd", "preprocess_bwd", "render_bwd") if k in kern}
+    if "camera_bwd" in kern and "preprocess_bwd" in kern:
+        out["camera_bwd_over_preprocess_bwd"] = kern["camera_bwd"]["avg_ms"] / kern["preprocess_bwd"]["avg_ms"]
+    out["visible_per_view"] = [float(x) / P for x in (rast(
+        means3D=scene["means3D"].detach(), means2D=means2D.detach(), opacities=scene["opacities"].detach(),
+        shs=scene["shs"].detach(), scales=scene["scales"].detach(),
+        rotations=scene["rotations"].detach())[1] > 0).sum(1).tolist()]
+    out["note"] = ("backward of one MultiViewRasterizer node, forward untimed; camera_bwd covers both camera kernels "
+                   "(one scope), the profile scopes include the forward's kernels of the same passes under their own ids")
     return out
 
 
