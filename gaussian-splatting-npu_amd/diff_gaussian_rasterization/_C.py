@@ -7,7 +7,10 @@ argument order, same returned tuples, same shape errors.  PyTorch only provides 
 memory and the current HIP stream; all compute runs in the HIP library.  There is no
 CPU fallback: a missing library, a non-GPU tensor or a HIP failure raises.
 """
+import collections
 import ctypes
+import functools
+import math
 import os
 
 import torch
@@ -19,15 +22,17 @@ _vp, _i, _f, _b, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_b
 
 
 def _load(path=LIB_PATH):
-    """The C ABI of the HIP library at `path` with its ctypes signatures.  The package loads only
+    """The C ABI of the HIP library at `path` with its ctypes signatures (tests/
+    test_binding_signatures.py holds them against include/gsr.h).  The package loads only
     LIB_PATH; tests/test_ref_alpha_exact.py passes its test-only GSR_REF_ALPHA build here."""
     if not os.path.exists(path):
         raise ImportError(
             f"diff_gaussian_rasterization: native library {path} is missing; build it with "
             "`make -C gaussian-splatting-npu_amd` (or __graft_entry__.build()). There is no CPU fallback.")
     lib = ctypes.CDLL(path)
-    lib.gsr_last_error.restype = ctypes.c_char_p
-    lib.gsr_version.restype = ctypes.c_char_p
+    for n in ("gsr_last_error", "gsr_version"):
+        getattr(lib, n).restype = ctypes.c_char_p
+        getattr(lib, n).argtypes = []
     for n in ("gsr_geometry_buffer_size", "gsr_binning_buffer_size"):
         getattr(lib, n).restype = _sz
         getattr(lib, n).argtypes = [_i]
@@ -111,12 +116,18 @@ def _check(rc):
 
 _contig_cache = {}  # small non-contiguous inputs (the transposed view matrices) -> contiguous copy
 # Per device: the last forward's num_rendered.  The next forward pre-allocates its binning buffer
-# from it (+25 % and 64K instances of headroom), so the native forward can run emission, sorts and
-# render straight after the num_rendered read-back instead of returning to Python to allocate
-# (the reference's binningBuffer resize lambda, rasterize_points.cu:27-33, rasterizer_impl.cu:286).
+# from it (_binning_capacity), so the native forward can run emission, sorts and render straight
+# after the num_rendered read-back instead of returning to Python to allocate (the reference's
+# binningBuffer resize lambda, rasterize_points.cu:27-33, rasterizer_impl.cu:286).
 _binning_hint = {}
 _binning_hint_views = {}  # per device: the last view batch's num_rendered per view
 views_reruns = 0  # batched forwards that outgrew their binning buffers and ran a second time
+
+
+def _binning_capacity(hint):
+    """Bytes of the binning buffer a forward pre-allocates for `hint` rendered instances (+25 % and
+    64K instances of headroom); 0 without a hint."""
+    return lib.gsr_binning_buffer_size(min(int(hint * 1.25) + 65536, 0x7FFFFFFF)) if hint is not None else 0
 
 
 def _contiguous(t):
@@ -160,11 +171,74 @@ def _require_gpu(t):
                            f"{t.device}. There is no CPU path.")
 
 
-def _sh_split(sh, dc):
-    """(M, has_dc): M = sh.size(1) -- with dc, the number of REST coefficients (0 if sh is empty)."""
+def _sh_split(sh, dc, P=None):
+    """(M, has_dc): M = sh.size(1) -- with dc, the number of REST coefficients (0 if sh is empty).
+    With P (the forwards), dc's shape is checked."""
     M = sh.size(1) if sh is not None and sh.numel() != 0 and sh.size(0) != 0 else 0
     has_dc = dc is not None and dc.numel() != 0
+    if has_dc and P is not None and (dc.dim() != 3 or dc.size(0) != P or dc.size(1) != 1 or dc.size(2) != 3):
+        raise RuntimeError("dc must have dimensions (num_points, 1, 3)")
     return M, has_dc
+
+
+# The per-view block of the batched entry points: R[] (host ints), `cams` = (viewmatrices[],
+# projmatrices[], campos[], tan_fovx[], tan_fovy[]) and the views' radii[] / geom[] / binning[] buffers.
+_Views = collections.namedtuple("_Views", "R cams radii geoms bins")
+
+
+class _Call:
+    """The native arguments of one Python call on `dev`: device pointers of checked tensors, host
+    arrays of them, and the argument blocks the rasterizer entry points share.  `keep` holds every
+    tensor pointed into (a contiguous copy made here must outlive the launch's enqueue)."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.keep = []
+
+    def p(self, t, name):
+        """_ptr(t): the device pointer of a float32 tensor on `dev`, NULL for an absent one."""
+        ptr, tt = _ptr(t, name, self.dev)
+        self.keep.append(tt)
+        return ptr
+
+    def array(self, ts, name=None):
+        """A host array of the device pointers of `ts` (a list, or a tensor's slices along dim 0): NULL
+        for None and for an empty tensor; with `name`, every tensor through `p`."""
+        if name is not None:
+            return (_vp * len(ts))(*[self.p(t, name) for t in ts])
+        self.keep.append(ts)
+        return (_vp * len(ts))(*[None if t is None or t.numel() == 0 else t.data_ptr() for t in ts])
+
+    def gaussians(self, means3D, dc, sh, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp):
+        """The Gaussians as every rasterizer entry point takes them after its sizes: means3D, dc, shs,
+        colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp."""
+        return (self.p(means3D, "means3D"), self.p(dc, "dc"), self.p(sh, "sh"), self.p(colors, "colors_precomp"),
+                self.p(opacities, "opacities"), self.p(scales, "scales"), float(scale_modifier),
+                self.p(rotations, "rotations"), self.p(cov3D_precomp, "cov3D_precomp"))
+
+    def cameras(self, viewmatrices, projmatrices, campos, tan_fovx, tan_fovy):
+        """_Views.cams of V views (per-view lists, or stacked tensors for the matrices and campos)."""
+        V = len(tan_fovx)
+        return (self.array(viewmatrices, "viewmatrix"), self.array(projmatrices, "projmatrix"),
+                self.array(campos, "campos"), (_f * V)(*[float(x) for x in tan_fovx]),
+                (_f * V)(*[float(x) for x in tan_fovy]))
+
+    def views(self, viewmatrices, projmatrices, campos, tan_fovx, tan_fovy, Rs, geomBuffers, binningBuffers,
+              radii=None):
+        """The per-view block of a batched backward, built once per Python call."""
+        return _Views((_i * len(Rs))(*[int(x) for x in Rs]),
+                      self.cameras(viewmatrices, projmatrices, campos, tan_fovx, tan_fovy),
+                      None if radii is None else self.array(radii), self.array(geomBuffers),
+                      self.array(binningBuffers))
+
+
+def _check_out(out, lead, P, H, W, dev):
+    """out= of the forwards: (color, radii, invdepth) of shapes lead + (3,H,W) / (P,) / (1,H,W)."""
+    for t, shape, dt in zip(out, ((3, H, W), (P,), (1, H, W)), (torch.float32, torch.int32, torch.float32)):
+        shape = lead + shape
+        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise RuntimeError(f"out: expected a contiguous {dt} tensor of shape {shape} on {dev}")
+    return out
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
@@ -189,42 +263,25 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 
     # every element of these is written by the HIP forward (radii by preprocess, pixels by render)
     if out is not None:
-        out_color, radii, out_invdepth = out
-        for t, shape, dt in ((out_color, (3, H, W), torch.float32), (radii, (P,), torch.int32),
-                             (out_invdepth, (1, H, W), torch.float32)):
-            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise RuntimeError(f"out: expected a contiguous {dt} tensor of shape {shape} on {dev}")
+        out_color, radii, out_invdepth = _check_out(out, (), P, H, W, dev)
     else:
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
         out_invdepth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
         out_color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-    M, has_dc = _sh_split(sh, dc)
-    if has_dc and (dc.dim() != 3 or dc.size(0) != P or dc.size(1) != 1 or dc.size(2) != 3):
-        raise RuntimeError("dc must have dimensions (num_points, 1, 3)")
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
+    M, _ = _sh_split(sh, dc, P)
+    a = _Call(dev)
     geom = torch.empty((lib.gsr_geometry_buffer_size(P),), dtype=torch.uint8, device=dev)
     img = torch.empty((lib.gsr_image_buffer_size(W, H),), dtype=torch.uint8, device=dev)
     stream = _stream(dev)
     nr = ctypes.c_int(0)
     rendered = ctypes.c_int(0)
-    hint = _binning_hint.get(dev)
-    cap = lib.gsr_binning_buffer_size(min(int(hint * 1.25) + 65536, 0x7FFFFFFF)) if hint is not None else 0
+    cap = _binning_capacity(_binning_hint.get(dev))
     binning = torch.empty((cap,), dtype=torch.uint8, device=dev) if cap else None
-    bg_p, means_p = p(background, "bg"), p(means3D, "means3D")
-    colors_p, op_p = p(colors, "colors_precomp"), p(opacity, "opacities")
-    sc_p, rot_p, cov_p = p(scales, "scales"), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp")
-    vm_p, pm_p = p(viewmatrix, "viewmatrix"), p(projmatrix, "projmatrix")
-    sh_p, cam_p = p(sh, "sh"), p(campos, "campos")
-    dc_p = p(dc, "dc") if has_dc else None
+    bg_p = a.p(background, "bg")
+    gauss = a.gaussians(means3D, dc, sh, colors, opacity, scales, scale_modifier, rotations, cov3D_precomp)
     _check(lib.gsr_forward_prealloc_dc(
         geom.data_ptr(), img.data_ptr(), binning.data_ptr() if cap else None, cap, P, int(degree), M, bg_p, W, H,
-        means_p, dc_p, sh_p, colors_p, op_p, sc_p, float(scale_modifier), rot_p, cov_p, vm_p, pm_p, cam_p,
+        *gauss, a.p(viewmatrix, "viewmatrix"), a.p(projmatrix, "projmatrix"), a.p(campos, "campos"),
         float(tan_fovx), float(tan_fovy), bool(prefiltered), bool(antialiasing), out_color.data_ptr(),
         out_invdepth.data_ptr(), radii.data_ptr(), bool(debug), stream, ctypes.byref(nr), ctypes.byref(rendered)))
     L = nr.value
@@ -235,7 +292,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     else:  # first call on this device, or the scene grew past the headroom
         binning = torch.empty((need,), dtype=torch.uint8, device=dev)
         _check(lib.gsr_forward_render(geom.data_ptr(), binning.data_ptr(), img.data_ptr(), P, L, bg_p, W, H,
-                                      colors_p, out_color.data_ptr(), out_invdepth.data_ptr(), radii.data_ptr(),
+                                      gauss[3], out_color.data_ptr(), out_invdepth.data_ptr(), radii.data_ptr(),
                                       bool(debug), stream))
     return L, out_color, radii, geom, binning, img, out_invdepth
 
@@ -252,35 +309,15 @@ def rasterize_gaussians_views(background, means3D, colors, opacity, scales, rota
     dev = means3D.device
     P, H, W = means3D.size(0), int(image_height), int(image_width)
     V = len(viewmatrices)
-    colors_out, radii_out, inv_out = out
-    for t, shape, dt in ((colors_out, (V, 3, H, W), torch.float32), (radii_out, (V, P), torch.int32),
-                         (inv_out, (V, 1, H, W), torch.float32)):
-        if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-            raise RuntimeError(f"out: expected a contiguous {dt} tensor of shape {shape} on {dev}")
+    colors_out, radii_out, inv_out = _check_out(out, (V,), P, H, W, dev)
     if P == 0:
         colors_out.zero_()
         radii_out.zero_()
         inv_out.zero_()
         e = torch.empty((0,), dtype=torch.uint8, device=dev)
         return [0] * V, [e] * V, [e] * V, [e] * V
-    M, has_dc = _sh_split(sh, dc)
-    if has_dc and (dc.dim() != 3 or dc.size(0) != P or dc.size(1) != 1 or dc.size(2) != 3):
-        raise RuntimeError("dc must have dimensions (num_points, 1, 3)")
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
-    def cont(ts, name):
-        res = []
-        for t in ts:
-            _, tt = _ptr(t, name, dev)
-            keep.append(tt)
-            res.append(tt)
-        return res
-
+    M, _ = _sh_split(sh, dc, P)
+    a = _Call(dev)
     gsz, isz = lib.gsr_geometry_buffer_size(P), lib.gsr_image_buffer_size(W, H)
     geoms = [torch.empty((gsz,), dtype=torch.uint8, device=dev) for _ in range(V)]
     imgs = [torch.empty((isz,), dtype=torch.uint8, device=dev) for _ in range(V)]
@@ -289,29 +326,21 @@ def rasterize_gaussians_views(background, means3D, colors, opacity, scales, rota
     # cameras to the batch's slots every step, so a per-slot hint would overflow (and rerun the
     # whole batch) whenever a slot's new view renders more than its old one did
     hints = _binning_hint_views.get(dev)
-    h = max(hints) if hints else _binning_hint.get(dev)
-    caps = [lib.gsr_binning_buffer_size(min(int(h * 1.25) + 65536, 0x7FFFFFFF))] * V if h is not None else [0] * V
-    bins = [torch.empty((c,), dtype=torch.uint8, device=dev) if c else None for c in caps]
-    bg_p, means_p = p(background, "bg"), p(means3D, "means3D")
-    colors_p, op_p = p(colors, "colors_precomp"), p(opacity, "opacities")
-    sc_p, rot_p, cov_p = p(scales, "scales"), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp")
-    sh_p = p(sh, "sh")
-    dc_p = p(dc, "dc") if has_dc else None
-    views, projs, cams = cont(viewmatrices, "viewmatrix"), cont(projmatrices, "projmatrix"), cont(campos, "campos")
-    stream = _stream(dev)
+    cap = _binning_capacity(max(hints) if hints else _binning_hint.get(dev))
+    bins = [torch.empty((cap,), dtype=torch.uint8, device=dev) if cap else None for _ in range(V)]
+    head = (V, P, int(degree), M, a.p(background, "bg"), W, H,
+            *a.gaussians(means3D, dc, sh, colors, opacity, scales, scale_modifier, rotations, cov3D_precomp),
+            *a.cameras(viewmatrices, projmatrices, campos, tan_fovx, tan_fovy), bool(prefiltered), bool(antialiasing),
+            a.array(geoms), a.array(imgs))
+    outs = (a.array(colors_out), a.array(inv_out), a.array(radii_out), bool(debug), _stream(dev))
     nr = (_i * V)()
     rendered = (_i * V)()
 
-    def run(caps):
-        _check(lib.gsr_forward_views(
-            V, P, int(degree), M, bg_p, W, H, means_p, dc_p, sh_p, colors_p, op_p, sc_p, float(scale_modifier), rot_p,
-            cov_p, _ptr_array(views), _ptr_array(projs), _ptr_array(cams), (_f * V)(*[float(t) for t in tan_fovx]),
-            (_f * V)(*[float(t) for t in tan_fovy]), bool(prefiltered), bool(antialiasing), _ptr_array(geoms),
-            _ptr_array(imgs), _ptr_array(bins), (_sz * V)(*caps), _ptr_array([colors_out[v] for v in range(V)]),
-            _ptr_array([inv_out[v] for v in range(V)]), _ptr_array([radii_out[v] for v in range(V)]), bool(debug),
-            stream, nr, rendered))
+    def run(bins):
+        _check(lib.gsr_forward_views(*head, a.array(bins), (_sz * V)(*[0 if b is None else b.numel() for b in bins]),
+                                     *outs, nr, rendered))
 
-    run(caps)
+    run(bins)
     Ls = [int(nr[v]) for v in range(V)]
     _binning_hint[dev] = max(Ls)
     _binning_hint_views[dev] = Ls
@@ -321,15 +350,81 @@ def rasterize_gaussians_views(background, means3D, colors, opacity, scales, rota
         global views_reruns
         views_reruns += 1
         bins = [torch.empty((lib.gsr_binning_buffer_size(L),), dtype=torch.uint8, device=dev) for L in Ls]
-        run([b.numel() for b in bins])
+        run(bins)
         if not all(rendered[v] for v in range(V)) or [int(nr[v]) for v in range(V)] != Ls:
             raise RuntimeError("diff_gaussian_rasterization (HIP): the repeated batch did not reproduce num_rendered")
     return Ls, geoms, bins, imgs
 
 
-# accumulate= keys -> gsr.h GSR_ACC_* bits
-ACC_BITS = {"means3D": 1, "dc": 2, "sh": 4, "opacities": 8, "scales": 16, "rotations": 32, "cov3D_precomp": 64,
-            "colors_precomp": 128}
+# The eight parameter gradients of the backward ops: accumulate= key, gsr.h GSR_ACC_* bit, and one
+# Gaussian's gradient as a function of M (its floats per Gaussian are the product; the gradient is
+# viewed as (P,) + that).  Fresh gradients are consecutive slices of ONE buffer in this order, which
+# starts with multiview.PARAM_ORDER / PARAM_ORDER_DC (means3D | [dc] | sh | opacity | scales |
+# rotations): autograd keeps these views as the leaves' .grad, so a multi-GPU step all-reduces the
+# buffer in place instead of gathering and scattering 236 B per Gaussian around the collective.
+# cov3D and colors_precomp follow, for the single view and the batch alike.
+_GRADS = (("means3D", 1, lambda M: (3,)), ("dc", 2, lambda M: (1, 3)), ("sh", 4, lambda M: (M, 3)),
+          ("opacities", 8, lambda M: (1,)), ("scales", 16, lambda M: (3,)), ("rotations", 32, lambda M: (4,)),
+          ("cov3D_precomp", 64, lambda M: (6,)), ("colors_precomp", 128, lambda M: (3,)))
+ACC_BITS = {name: bit for name, bit, _ in _GRADS}  # accumulate= keys -> GSR_ACC_* bits
+# The order after dL_dmeans2D of the tuple the backward ops return (dL_ddc only with dc), and of the
+# gradient pointers the batched entry points take.
+_RESULT_ORDER = ("colors_precomp", "opacities", "means3D", "cov3D_precomp", "dc", "sh", "scales", "rotations")
+
+
+@functools.lru_cache(maxsize=16)
+def _grad_shapes(P, M):
+    """{key: (shape, its contiguous strides, floats)} of the _GRADS gradients of P Gaussians (the
+    host path of every backward: worked out once per size)."""
+    out = {}
+    for name, _, row in _GRADS:
+        shape = (P,) + row(M)
+        strides = tuple(math.prod(shape[d + 1:]) for d in range(len(shape)))
+        out[name] = (shape, strides, math.prod(shape))
+    return out
+
+
+def _check_accumulate(accumulate, shapes, has_dc, dev):
+    """accumulate= of a backward op as a dict, every target checked against its gradient's size."""
+    acc = dict(accumulate or {})
+    for k, t in acc.items():
+        if k not in shapes:
+            raise RuntimeError(f"accumulate: unknown gradient {k!r}")
+        n = shapes[k][2]
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise RuntimeError(f"accumulate[{k!r}] must be a contiguous float32 tensor of {n} elements on {dev}")
+    if "dc" in acc and not has_dc:
+        raise RuntimeError("accumulate['dc'] given without dc")
+    return acc
+
+
+def _param_grads(P, M, has_dc, accumulate, dev):
+    """The parameter gradients a backward writes: ({key: tensor, None for dc without dc}, the checked
+    accumulate dict, its GSR_ACC_* mask).  A key of `accumulate` gets the caller's target, the
+    others consecutive pieces of one fresh buffer, in _GRADS order (the kernel writes every element,
+    zeros for culled Gaussians)."""
+    shapes = _grad_shapes(P, M)
+    acc = _check_accumulate(accumulate, shapes, has_dc, dev)
+    fresh = [k for k in shapes if k not in acc and (has_dc or k != "dc")]
+    buf = torch.empty((sum(shapes[k][2] for k in fresh),), dtype=torch.float32, device=dev)
+    r, off = {}, 0
+    for k, (shape, strides, n) in shapes.items():
+        if k in fresh:
+            r[k] = buf.as_strided(shape, strides, off)
+            off += n
+        else:
+            r[k] = acc[k].view(shape) if k in acc else None
+    return r, acc, sum(ACC_BITS[k] for k in acc)
+
+
+def _grad_ptrs(r, M):
+    """The gradients' device pointers in _RESULT_ORDER (NULL: dL_ddc without dc, dL_dsh for M = 0)."""
+    return [None if r[k] is None or (k == "sh" and not M) else r[k].data_ptr() for k in _RESULT_ORDER]
+
+
+def _grad_result(dL_dmeans2D, r, acc, has_dc):
+    """The backward ops' tuple: None in place of a gradient the kernel added into its target."""
+    return (dL_dmeans2D,) + tuple(None if k in acc else r[k] for k in _RESULT_ORDER if has_dc or k != "dc")
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, opacities, scales, rotations, scale_modifier,
@@ -349,144 +444,73 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, opacities, 
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
     M, has_dc = _sh_split(sh, dc)
-    # Render-pass gradients (one allocation): mean2D 3 | colors 3 | conic 4 | invdepth 1.
+    # Render-pass gradients (one allocation): mean2D 3 | conic 4 | invdepth 1.
     # The HIP backward writes every element (no atomics, no pre-zeroing needed).
-    rbuf = torch.empty((P * 11,), dtype=torch.float32, device=dev)
+    rbuf = torch.empty((P * 8,), dtype=torch.float32, device=dev)
     dL_dmeans2D = rbuf[0:3 * P].view(P, 3)
-    dL_dcolors = rbuf[3 * P:6 * P].view(P, 3)
-    dL_dconic = rbuf[6 * P:10 * P].view(P, 2, 2)
+    dL_dconic = rbuf[3 * P:7 * P].view(P, 2, 2)
     has_inv = dL_dout_invdepth is not None and dL_dout_invdepth.numel() != 0 and dL_dout_invdepth.size(0) != 0
-    dL_dinvdepths = rbuf[10 * P:11 * P].view(P, 1)
-    # Parameter gradients, fully written by the HIP kernel (zeros for culled Gaussians), in ONE
-    # buffer laid out as multiview.PARAM_ORDER (means3D | sh | opacity | scales | rotations) then
-    # cov3D: autograd keeps these views as the leaves' .grad, so a multi-GPU step all-reduces the
-    # buffer in place instead of gathering and scattering 236 B per Gaussian around the collective.
-    # With dc, its gradient sits between means3D and the rest (multiview.PARAM_ORDER_DC).
-    acc = dict(accumulate or {})
-    for k, t in acc.items():
-        n = {"means3D": 3 * P, "dc": 3 * P, "sh": 3 * M * P, "opacities": P, "scales": 3 * P, "rotations": 4 * P,
-             "cov3D_precomp": 6 * P, "colors_precomp": 3 * P}.get(k)
-        if n is None:
-            raise RuntimeError(f"accumulate: unknown gradient {k!r}")
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise RuntimeError(f"accumulate[{k!r}] must be a contiguous float32 tensor of {n} elements on {dev}")
-    if "dc" in acc and not has_dc:
-        raise RuntimeError("accumulate['dc'] given without dc")
-    sizes = [0 if "means3D" in acc else 3 * P, 3 * P if has_dc and "dc" not in acc else 0,
-             0 if "sh" in acc else 3 * M * P, 0 if "opacities" in acc else P, 0 if "scales" in acc else 3 * P,
-             0 if "rotations" in acc else 4 * P, 0 if "cov3D_precomp" in acc else 6 * P]
-    parts = torch.split(torch.empty((sum(sizes),), dtype=torch.float32, device=dev), sizes)
-    dL_dmeans3D = acc.get("means3D", parts[0]).view(P, 3)
-    dL_ddc = acc.get("dc", parts[1]).view(P, 1, 3) if has_dc else None
-    dL_dsh = acc.get("sh", parts[2]).view(P, M, 3)
-    dL_dopacity = acc.get("opacities", parts[3]).view(P, 1)
-    dL_dscales = acc.get("scales", parts[4]).view(P, 3)
-    dL_drotations = acc.get("rotations", parts[5]).view(P, 4)
-    dL_dcov3D = acc.get("cov3D_precomp", parts[6]).view(P, 6)
-    if "colors_precomp" in acc:
-        dL_dcolors = acc["colors_precomp"].view(P, 3)
-
-    def result():
-        r = {"means3D": dL_dmeans3D, "dc": dL_ddc, "sh": dL_dsh, "opacities": dL_dopacity, "scales": dL_dscales,
-             "rotations": dL_drotations, "cov3D_precomp": dL_dcov3D, "colors_precomp": dL_dcolors}
-        r = {k: (None if k in acc else v) for k, v in r.items()}
-        if has_dc:
-            return (dL_dmeans2D, r["colors_precomp"], r["opacities"], r["means3D"], r["cov3D_precomp"], r["dc"],
-                    r["sh"], r["scales"], r["rotations"])
-        return (dL_dmeans2D, r["colors_precomp"], r["opacities"], r["means3D"], r["cov3D_precomp"], r["sh"],
-                r["scales"], r["rotations"])
-
+    dL_dinvdepths = rbuf[7 * P:8 * P].view(P, 1)
+    r, acc, mask = _param_grads(P, M, has_dc, accumulate, dev)
     if P == 0:
-        return result()
-
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
-    dpix = p(dL_dout_color, "dL_dout_color")
-    dinv = p(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None
-    mask = 0
-    for k in acc:
-        mask |= ACC_BITS[k]
+        return _grad_result(dL_dmeans2D, r, acc, has_dc)
+    a = _Call(dev)
+    g_color, g_opacity, *g_rest = _grad_ptrs(r, M)
     _check(lib.gsr_backward_dc_acc(
-        P, int(degree), M, int(R), p(background, "bg"), W, H, p(means3D, "means3D"),
-        p(dc, "dc") if has_dc else None, p(sh, "sh"),
-        p(colors, "colors_precomp"), p(opacities, "opacities"), p(scales, "scales"), float(scale_modifier),
-        p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"), p(viewmatrix, "viewmatrix"),
-        p(projmatrix, "projmatrix"), p(campos, "campos"), float(tan_fovx), float(tan_fovy), radii.data_ptr(),
-        geomBuffer.data_ptr(), binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
-        dpix, dinv, dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(), dL_dcolors.data_ptr(),
-        dL_dinvdepths.data_ptr() if has_inv else None, dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-        dL_ddc.data_ptr() if has_dc else None, dL_dsh.data_ptr() if M else None, dL_dscales.data_ptr(),
-        dL_drotations.data_ptr(), bool(antialiasing), bool(debug), mask, _stream(dev)))
-    return result()
+        P, int(degree), M, int(R), a.p(background, "bg"), W, H,
+        *a.gaussians(means3D, dc, sh, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp),
+        a.p(viewmatrix, "viewmatrix"), a.p(projmatrix, "projmatrix"), a.p(campos, "campos"), float(tan_fovx),
+        float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(),
+        binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
+        a.p(dL_dout_color, "dL_dout_color"), a.p(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
+        dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), g_opacity, g_color,
+        dL_dinvdepths.data_ptr() if has_inv else None, *g_rest, bool(antialiasing), bool(debug), mask, _stream(dev)))
+    return _grad_result(dL_dmeans2D, r, acc, has_dc)
 
 
-def _ptr_array(ts):
-    return (_vp * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
-
-
-def _views_grads(P, M, V, has_dc, accumulate, dev):
-    """Outputs of a multi-view backward: (V,P,3) screen-space gradients and the summed parameter
-    gradients (fresh buffers, or the caller's `accumulate` targets), plus the GSR_ACC_* mask."""
-    acc = dict(accumulate or {})
-    for k, t in acc.items():
-        n = {"means3D": 3 * P, "dc": 3 * P, "sh": 3 * M * P, "opacities": P, "scales": 3 * P, "rotations": 4 * P,
-             "cov3D_precomp": 6 * P, "colors_precomp": 3 * P}.get(k)
-        if n is None:
-            raise RuntimeError(f"accumulate: unknown gradient {k!r}")
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise RuntimeError(f"accumulate[{k!r}] must be a contiguous float32 tensor of {n} elements on {dev}")
+def _backward_views(render, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp,
+                    viewmatrices, projmatrices, tan_fovx, tan_fovy, W, H, sh, degree, campos, geomBuffers, Rs,
+                    binningBuffers, has_inv, antialiasing, debug, dc, accumulate, on_chunk):
+    """The batched backward behind rasterize_gaussians_backward_views (render = (background,
+    imageBuffers, dL_dout_colors, dL_dout_invdepths or None): the views' BACKWARD::render runs here)
+    and rasterize_gaussians_preprocess_backward_views (render = None: it already ran).  Without
+    on_chunk one native call (gsr_backward_views / gsr_backward_preprocess_views); with on_chunk =
+    (chunks, fn) gsr_backward_render_views if `render`, then gsr_backward_preprocess_views_range over
+    `chunks` Gaussian ranges (multiples of 256, the batched kernel's workgroup width), fn(g0, g1,
+    grads) after each."""
+    _require_gpu(means3D)
+    dev = means3D.device
+    P, V = means3D.size(0), len(geomBuffers)
+    M, has_dc = _sh_split(sh, dc)
     dL_dmeans2D = torch.empty((V, P, 3), dtype=torch.float32, device=dev)
-    sizes = [0 if "means3D" in acc else 3 * P, 3 * P if has_dc and "dc" not in acc else 0,
-             0 if "sh" in acc else 3 * M * P, 0 if "opacities" in acc else P, 0 if "scales" in acc else 3 * P,
-             0 if "rotations" in acc else 4 * P, 0 if "cov3D_precomp" in acc else 6 * P,
-             0 if "colors_precomp" in acc else 3 * P]
-    parts = torch.split(torch.empty((sum(sizes),), dtype=torch.float32, device=dev), sizes)
-    r = {"means3D": acc.get("means3D", parts[0]).view(P, 3),
-         "dc": acc.get("dc", parts[1]).view(P, 1, 3) if has_dc else None,
-         "sh": acc.get("sh", parts[2]).view(P, M, 3), "opacities": acc.get("opacities", parts[3]).view(P, 1),
-         "scales": acc.get("scales", parts[4]).view(P, 3), "rotations": acc.get("rotations", parts[5]).view(P, 4),
-         "cov3D_precomp": acc.get("cov3D_precomp", parts[6]).view(P, 6),
-         "colors_precomp": acc.get("colors_precomp", parts[7]).view(P, 3)}
-    mask = 0
-    for k in acc:
-        mask |= ACC_BITS[k]
-    return dL_dmeans2D, r, acc, mask
-
-
-def _views_result(dL_dmeans2D, r, acc, has_dc):
-    r = {k: (None if k in acc else v) for k, v in r.items()}
-    if has_dc:
-        return (dL_dmeans2D, r["colors_precomp"], r["opacities"], r["means3D"], r["cov3D_precomp"], r["dc"], r["sh"],
-                r["scales"], r["rotations"])
-    return (dL_dmeans2D, r["colors_precomp"], r["opacities"], r["means3D"], r["cov3D_precomp"], r["sh"],
-            r["scales"], r["rotations"])
-
-
-def _preprocess_views_chunks(on_chunk, V, P, degree, M, Rs, W, H, means_p, dc_p, sh_p, colors_p, op_p, sc_p,
-                             scale_modifier, rot_p, cov_p, views, projs, cams, tan_fovx, tan_fovy, radii, geomBuffers,
-                             binningBuffers, has_inv, dL_dmeans2D, r, has_dc, antialiasing, debug, mask, acc, dev):
-    """gsr_backward_preprocess_views_range over `chunks` Gaussian ranges (multiples of 256, the
-    batched kernel's workgroup width), fn(g0, g1, grads) after each."""
+    r, acc, mask = _param_grads(P, M, has_dc, accumulate, dev)
+    a = _Call(dev)
+    vb = a.views(viewmatrices, projmatrices, campos, tan_fovx, tan_fovy, Rs, geomBuffers, binningBuffers, radii)
+    sizes = (V, P, int(degree), M, vb.R)
+    gauss = a.gaussians(means3D, dc, sh, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp)
+    state = (*vb.cams, vb.radii, vb.geoms, vb.bins)
+    grads = (a.array(dL_dmeans2D), *_grad_ptrs(r, M), bool(antialiasing), bool(debug), mask)
+    if render is not None:
+        background, imageBuffers, dL_dout_colors, dL_dout_invdepths = render
+        frame = (a.p(background, "bg"), W, H)
+        pix = (a.array(imageBuffers), a.array(dL_dout_colors, "dL_dout_color"),
+               a.array(dL_dout_invdepths, "dL_dout_invdepth") if has_inv else None)
+        if on_chunk is None:
+            _check(lib.gsr_backward_views(*sizes, *frame, *gauss, *state, *pix, *grads, _stream(dev)))
+            return _grad_result(dL_dmeans2D, r, acc, has_dc)
+        _check(lib.gsr_backward_render_views(V, P, vb.R, *frame, vb.geoms, vb.bins, *pix, bool(debug), _stream(dev)))
+    preprocess = (*sizes, int(W), int(H), *gauss, *state, bool(has_inv), *grads)
+    if on_chunk is None:
+        _check(lib.gsr_backward_preprocess_views(*preprocess, _stream(dev)))
+        return _grad_result(dL_dmeans2D, r, acc, has_dc)
     chunks, fn = on_chunk
     step = max(256, -(-P // max(1, int(chunks)) // 256) * 256)
-    grads = {k: t for k, t in r.items() if t is not None}
+    given = {k: t for k, t in r.items() if t is not None}
     for g0 in range(0, P, step):
         g1 = min(P, g0 + step)
-        _check(lib.gsr_backward_preprocess_views_range(
-            V, P, int(degree), M, (_i * V)(*[int(x) for x in Rs]), int(W), int(H), means_p, dc_p, sh_p, colors_p,
-            op_p, sc_p, float(scale_modifier), rot_p, cov_p, _ptr_array(views), _ptr_array(projs), _ptr_array(cams),
-            (_f * V)(*[float(x) for x in tan_fovx]), (_f * V)(*[float(x) for x in tan_fovy]), _ptr_array(radii),
-            _ptr_array(geomBuffers), _ptr_array([b if b.numel() else None for b in binningBuffers]), bool(has_inv),
-            _ptr_array([dL_dmeans2D[v] for v in range(V)]), r["colors_precomp"].data_ptr(),
-            r["opacities"].data_ptr(), r["means3D"].data_ptr(), r["cov3D_precomp"].data_ptr(),
-            r["dc"].data_ptr() if has_dc else None, r["sh"].data_ptr() if M else None, r["scales"].data_ptr(),
-            r["rotations"].data_ptr(), bool(antialiasing), bool(debug), mask, g0, g1, _stream(dev)))
-        fn(g0, g1, grads)
+        _check(lib.gsr_backward_preprocess_views_range(*preprocess, g0, g1, _stream(dev)))
+        fn(g0, g1, given)
+    return _grad_result(dL_dmeans2D, r, acc, has_dc)
 
 
 def rasterize_gaussians_backward_views(background, means3D, radii, colors, opacities, scales, rotations,
@@ -504,76 +528,28 @@ def rasterize_gaussians_backward_views(background, means3D, radii, colors, opaci
     grads) is called after each launch is enqueued, grads = {input name: its gradient tensor (P,...)}
     (the caller's accumulate targets or the fresh buffers): rows [g0, g1) are final from then on in
     stream order (multiview.overlapped_allreduce)."""
-    _require_gpu(means3D)
-    dev = means3D.device
-    P = means3D.size(0)
     V = len(geomBuffers)
     H, W = dL_dout_colors.size(2), dL_dout_colors.size(3)
-    M, has_dc = _sh_split(sh, dc)
     has_inv = dL_dout_invdepths is not None and dL_dout_invdepths.numel() != 0
     if dL_dout_colors.shape != (V, 3, H, W) or (has_inv and dL_dout_invdepths.shape != (V, 1, H, W)):
         raise RuntimeError("dL_dout_colors must be (V,3,H,W) and dL_dout_invdepths (V,1,H,W)")
-    dL_dmeans2D, r, acc, mask = _views_grads(P, M, V, has_dc, accumulate, dev)
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
-    def cont(ts, name):
-        out = []
-        for t in ts:
-            ptr, tt = _ptr(t, name, dev)
-            keep.append(tt)
-            out.append(tt)
-        return out
-
-    views = cont(viewmatrices, "viewmatrix")
-    projs = cont(projmatrices, "projmatrix")
-    cams = cont(campos, "campos")
-    dpix = [dL_dout_colors[v].contiguous() for v in range(V)]
-    dinv = [dL_dout_invdepths[v].contiguous() for v in range(V)] if has_inv else None
-    keep.extend(dpix)
-    if on_chunk is not None:
-        _check(lib.gsr_backward_render_views(
-            V, P, (_i * V)(*[int(x) for x in Rs]), p(background, "bg"), W, H, _ptr_array(geomBuffers),
-            _ptr_array([b if b.numel() else None for b in binningBuffers]), _ptr_array(imageBuffers),
-            _ptr_array(dpix), _ptr_array(dinv) if has_inv else None, bool(debug), _stream(dev)))
-        _preprocess_views_chunks(on_chunk, V, P, degree, M, Rs, W, H, p(means3D, "means3D"),
-                                 p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"),
-                                 p(opacities, "opacities"), p(scales, "scales"), scale_modifier,
-                                 p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"), views, projs, cams,
-                                 tan_fovx, tan_fovy, radii, geomBuffers, binningBuffers, has_inv, dL_dmeans2D, r,
-                                 has_dc, antialiasing, debug, mask, acc, dev)
-        return _views_result(dL_dmeans2D, r, acc, has_dc)
-    _check(lib.gsr_backward_views(
-        V, P, int(degree), M, (_i * V)(*[int(x) for x in Rs]), p(background, "bg"), W, H, p(means3D, "means3D"),
-        p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"), p(opacities, "opacities"),
-        p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"),
-        _ptr_array(views), _ptr_array(projs), _ptr_array(cams), (_f * V)(*[float(x) for x in tan_fovx]),
-        (_f * V)(*[float(x) for x in tan_fovy]), _ptr_array(radii), _ptr_array(geomBuffers),
-        _ptr_array([b if b.numel() else None for b in binningBuffers]), _ptr_array(imageBuffers),
-        _ptr_array(dpix), _ptr_array(dinv) if has_inv else None, _ptr_array([dL_dmeans2D[v] for v in range(V)]),
-        r["colors_precomp"].data_ptr(), r["opacities"].data_ptr(), r["means3D"].data_ptr(),
-        r["cov3D_precomp"].data_ptr(), r["dc"].data_ptr() if has_dc else None, r["sh"].data_ptr() if M else None,
-        r["scales"].data_ptr(), r["rotations"].data_ptr(), bool(antialiasing), bool(debug), mask, _stream(dev)))
-    return _views_result(dL_dmeans2D, r, acc, has_dc)
+    return _backward_views((background, imageBuffers, dL_dout_colors, dL_dout_invdepths), means3D, radii, colors,
+                           opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+                           tan_fovx, tan_fovy, W, H, sh, degree, campos, geomBuffers, Rs, binningBuffers, has_inv,
+                           antialiasing, debug, dc, accumulate, on_chunk)
 
 
 def rasterize_gaussians_render_backward(background, P, R, geomBuffer, binningBuffer, imageBuffer, dL_dout_color,
                                         dL_dout_invdepth, debug):
     """BACKWARD::render of one view (gsr_backward_render): its per-(tile, Gaussian) gradient
     records into binningBuffer, for rasterize_gaussians_preprocess_backward_views later."""
-    dev = dL_dout_color.device
+    a = _Call(dL_dout_color.device)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
     has_inv = dL_dout_invdepth is not None and dL_dout_invdepth.numel() != 0
-    bg_p, bg = _ptr(background, "bg", dev)
-    dpix, dpix_t = _ptr(dL_dout_color, "dL_dout_color", dev)
-    dinv, dinv_t = _ptr(dL_dout_invdepth, "dL_dout_invdepth", dev) if has_inv else (None, None)
-    _check(lib.gsr_backward_render(int(P), int(R), bg_p, W, H, geomBuffer.data_ptr(),
+    _check(lib.gsr_backward_render(int(P), int(R), a.p(background, "bg"), W, H, geomBuffer.data_ptr(),
                                    binningBuffer.data_ptr() if binningBuffer.numel() else None,
-                                   imageBuffer.data_ptr(), dpix, dinv, bool(debug), _stream(dev)))
+                                   imageBuffer.data_ptr(), a.p(dL_dout_color, "dL_dout_color"),
+                                   a.p(dL_dout_invdepth, "dL_dout_invdepth"), bool(debug), _stream(a.dev)))
     return has_inv
 
 
@@ -585,48 +561,10 @@ def rasterize_gaussians_preprocess_backward_views(means3D, radii, colors, opacit
     """BACKWARD::preprocess of V views whose render backward already ran
     (gsr_backward_preprocess_views); returns what rasterize_gaussians_backward_views returns;
     on_chunk as there."""
-    _require_gpu(means3D)
-    dev = means3D.device
-    P = means3D.size(0)
-    V = len(geomBuffers)
-    M, has_dc = _sh_split(sh, dc)
-    dL_dmeans2D, r, acc, mask = _views_grads(P, M, V, has_dc, accumulate, dev)
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
-    def cont(ts, name):
-        out = []
-        for t in ts:
-            _, tt = _ptr(t, name, dev)
-            keep.append(tt)
-            out.append(tt)
-        return out
-
-    views, projs, cams = cont(viewmatrices, "viewmatrix"), cont(projmatrices, "projmatrix"), cont(campos, "campos")
-    if on_chunk is not None:
-        _preprocess_views_chunks(on_chunk, V, P, degree, M, Rs, image_width, image_height, p(means3D, "means3D"),
-                                 p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"),
-                                 p(opacities, "opacities"), p(scales, "scales"), scale_modifier,
-                                 p(rotations, "rotations"), p(cov3D_precomp, "cov3D_precomp"), views, projs, cams,
-                                 tan_fovx, tan_fovy, radii, geomBuffers, binningBuffers, has_invdepth, dL_dmeans2D, r,
-                                 has_dc, antialiasing, debug, mask, acc, dev)
-        return _views_result(dL_dmeans2D, r, acc, has_dc)
-    _check(lib.gsr_backward_preprocess_views(
-        V, P, int(degree), M, (_i * V)(*[int(x) for x in Rs]), int(image_width), int(image_height),
-        p(means3D, "means3D"), p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"),
-        p(opacities, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
-        p(cov3D_precomp, "cov3D_precomp"), _ptr_array(views), _ptr_array(projs), _ptr_array(cams),
-        (_f * V)(*[float(x) for x in tan_fovx]), (_f * V)(*[float(x) for x in tan_fovy]), _ptr_array(radii),
-        _ptr_array(geomBuffers), _ptr_array([b if b.numel() else None for b in binningBuffers]), bool(has_invdepth),
-        _ptr_array([dL_dmeans2D[v] for v in range(V)]), r["colors_precomp"].data_ptr(), r["opacities"].data_ptr(),
-        r["means3D"].data_ptr(), r["cov3D_precomp"].data_ptr(), r["dc"].data_ptr() if has_dc else None,
-        r["sh"].data_ptr() if M else None, r["scales"].data_ptr(), r["rotations"].data_ptr(), bool(antialiasing),
-        bool(debug), mask, _stream(dev)))
-    return _views_result(dL_dmeans2D, r, acc, has_dc)
+    return _backward_views(None, means3D, radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp,
+                           viewmatrices, projmatrices, tan_fovx, tan_fovy, image_width, image_height, sh, degree,
+                           campos, geomBuffers, Rs, binningBuffers, has_invdepth, antialiasing, debug, dc, accumulate,
+                           on_chunk)
 
 
 def _camera_check(name, t, shape):
@@ -680,27 +618,17 @@ def backward_camera_views(means3D, colors, opacities, scales, rotations, scale_m
     dev = _act_device([(name, t) for name, t, _ in cams + outs if t is not None])
     _require_gpu(means3D)
     P = means3D.size(0)
-    M, has_dc = _sh_split(sh, dc)
+    M, _ = _sh_split(sh, dc)
     grads = [t if t is not None else torch.empty(shape, dtype=torch.float32, device=dev) for _, t, shape in outs]
-    keep = []
-
-    def p(t, name):
-        ptr, tt = _ptr(t, name, dev)
-        keep.append(tt)
-        return ptr
-
+    a = _Call(dev)
+    vb = a.views(viewmatrices, projmatrices, campos, tan_fovx, tan_fovy, Rs, geomBuffers, binningBuffers)
     workspace = torch.empty((camera_grad_workspace_size(V, P),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _check(lib.gsr_backward_camera_views(
-            V, P, int(degree), M, (_i * V)(*[int(x) for x in Rs]), int(image_width), int(image_height),
-            p(means3D, "means3D"), p(dc, "dc") if has_dc else None, p(sh, "sh"), p(colors, "colors_precomp"),
-            p(opacities, "opacities"), p(scales, "scales"), float(scale_modifier), p(rotations, "rotations"),
-            p(cov3D_precomp, "cov3D_precomp"), _ptr_array([viewmatrices[v] for v in range(V)]),
-            _ptr_array([projmatrices[v] for v in range(V)]), _ptr_array([campos[v] for v in range(V)]),
-            (_f * V)(*[float(x) for x in tan_fovx]), (_f * V)(*[float(x) for x in tan_fovy]),
-            _ptr_array(geomBuffers), _ptr_array([b if b.numel() else None for b in binningBuffers]),
-            bool(has_invdepth), bool(antialiasing), workspace.data_ptr(), grads[0].data_ptr(), grads[1].data_ptr(),
-            grads[2].data_ptr(), bool(debug), _stream(dev)))
+            V, P, int(degree), M, vb.R, int(image_width), int(image_height),
+            *a.gaussians(means3D, dc, sh, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp),
+            *vb.cams, vb.geoms, vb.bins, bool(has_invdepth), bool(antialiasing), workspace.data_ptr(),
+            grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), bool(debug), _stream(dev)))
     return tuple(grads)
 
 
@@ -712,6 +640,13 @@ def _adam_check(param, param_grad, exp_avg, exp_avg_sq, N, M, dev):
             raise RuntimeError(f"adamUpdate: {name} has {t.numel()} elements, expected N*M = {int(N) * int(M)}")
 
 
+def _adam_visible(visible, N, dev):
+    """The visibility mask of the Adam calls, contiguous: N bool flags on `dev`."""
+    if visible.device != dev or visible.dtype != torch.bool or visible.numel() != int(N):
+        raise RuntimeError(f"adamUpdate: visible must be a bool tensor of N = {int(N)} flags on {dev}")
+    return visible.contiguous()
+
+
 def adam_update_groups(groups, visible, b1, b2, N):
     """One launch for several (param, grad, exp_avg, exp_avg_sq, lr, eps) groups sharing the
     visibility mask of N Gaussians (SparseGaussianAdam.step); M = param.numel() // N per group."""
@@ -719,9 +654,7 @@ def adam_update_groups(groups, visible, b1, b2, N):
         return
     dev = groups[0][0].device
     _require_gpu(groups[0][0])
-    if visible.device != dev or visible.dtype != torch.bool or visible.numel() != int(N):
-        raise RuntimeError(f"adamUpdate: visible must be a bool tensor of N = {int(N)} flags on {dev}")
-    visible = visible.contiguous()
+    visible = _adam_visible(visible, N, dev)
     n = len(groups)
     Ms = [g[0].numel() // int(N) if int(N) else 0 for g in groups]
     for (p, gr, m, v, _, _), M in zip(groups, Ms):
@@ -738,12 +671,18 @@ def adamUpdate(param, param_grad, exp_avg, exp_avg_sq, visible, lr, b1, b2, eps,
     _require_gpu(param)
     dev = param.device
     _adam_check(param, param_grad, exp_avg, exp_avg_sq, N, M, dev)
-    if visible.device != dev or visible.dtype != torch.bool or visible.numel() != int(N):
-        raise RuntimeError(f"adamUpdate: visible must be a bool tensor of N = {int(N)} flags on {dev}")
-    visible = visible.contiguous()
+    visible = _adam_visible(visible, N, dev)
     _check(lib.gsr_adam_update(param.data_ptr(), param_grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
                                visible.data_ptr(), float(lr), float(b1), float(b2), float(eps), int(N), int(M),
                                _stream(dev)))
+
+
+def _column_stride(name, t, P, dev):
+    """The row stride in floats (>= 1) of a float32 column of P rows -- (P,) or (P,1), any row stride:
+    a column of one (P,2) buffer, or a tensor of its own (xyz_gradient_accum, denom)."""
+    if t.device != dev or t.dtype != torch.float32 or t.numel() != P or t.dim() not in (1, 2) or t.size(0) != P:
+        raise RuntimeError(f"{name} must be a float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
+    return max(1, t.stride(0))
 
 
 def densification_stats(viewspace_grads, radii, max_radii2D, accum, denom, visible_count=None):
@@ -760,11 +699,7 @@ def densification_stats(viewspace_grads, radii, max_radii2D, accum, denom, visib
         raise RuntimeError(f"radii must be an int32 tensor of shape {(V, P)} on {dev}")
     if viewspace_grads.dtype != torch.float32:
         raise RuntimeError("viewspace_grads must be float32")
-    rows = []
-    for name, t in (("xyz_gradient_accum", accum), ("denom", denom)):
-        if t.device != dev or t.dtype != torch.float32 or t.numel() != P or t.dim() not in (1, 2) or t.size(0) != P:
-            raise RuntimeError(f"{name} must be a float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
-        rows.append(max(1, t.stride(0)))
+    rows = [_column_stride(name, t, P, dev) for name, t in (("xyz_gradient_accum", accum), ("denom", denom))]
     flat = [("max_radii2D", max_radii2D)] + ([("visible_count", visible_count)] if visible_count is not None else [])
     for name, t in flat:
         if t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != (P,) or not t.is_contiguous():
@@ -883,11 +818,7 @@ def densify_plan(accum, denom, scaling, opacity, max_grad, dense_extent, min_opa
     if (opacity.device != dev or opacity.dtype != torch.float32 or opacity.numel() != P or opacity.dim() not in (1, 2)
             or opacity.size(0) != P or not opacity.is_contiguous()):
         raise RuntimeError(f"opacity must be a contiguous float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
-    rows = []
-    for name, t in (("xyz_gradient_accum", accum), ("denom", denom)):
-        if t.device != dev or t.dtype != torch.float32 or t.numel() != P or t.dim() not in (1, 2) or t.size(0) != P:
-            raise RuntimeError(f"{name} must be a float32 tensor of shape ({P},) or ({P}, 1) on {dev}")
-        rows.append(max(1, t.stride(0)))
+    rows = [_column_stride(name, t, P, dev) for name, t in (("xyz_gradient_accum", accum), ("denom", denom))]
     if int(N) < 1:
         raise RuntimeError("N must be >= 1")
     counts = (_i * 4)()
@@ -1060,14 +991,12 @@ def rows_scatter(tensors, rows, U, compact, window=None):
 def mark_visible(means3D, viewmatrix, projmatrix):
     """markVisible (rasterize_points.cu:225-244)."""
     _require_gpu(means3D)
-    dev = means3D.device
+    a = _Call(means3D.device)
     P = means3D.size(0)
-    present = torch.zeros((P,), dtype=torch.bool, device=dev)
+    present = torch.zeros((P,), dtype=torch.bool, device=a.dev)
     if P != 0:
-        m, mt = _ptr(means3D, "means3D", dev)
-        v, vt = _ptr(viewmatrix, "viewmatrix", dev)
-        pr, pt = _ptr(projmatrix, "projmatrix", dev)
-        _check(lib.gsr_mark_visible(P, m, v, pr, present.data_ptr(), _stream(dev)))
+        _check(lib.gsr_mark_visible(P, a.p(means3D, "means3D"), a.p(viewmatrix, "viewmatrix"),
+                                    a.p(projmatrix, "projmatrix"), present.data_ptr(), _stream(a.dev)))
     return present
 
 

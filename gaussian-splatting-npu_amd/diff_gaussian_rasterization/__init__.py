@@ -118,6 +118,57 @@ def _accumulation_target(t):
     return g
 
 
+def _named_inputs(means3D, dc, sh, opacities, scales, rotations, cov3D_precomp, colors_precomp):
+    """The Gaussian inputs of a rasterizer call under the keys of _C.ACC_BITS."""
+    return {"means3D": means3D, "dc": dc, "sh": sh, "opacities": opacities, "scales": scales, "rotations": rotations,
+            "cov3D_precomp": cov3D_precomp, "colors_precomp": colors_precomp}
+
+
+class _Fenced:
+    """Context of one launch that adds into `targets` ({key: an existing .grad buffer}) on the current
+    stream of `dev`; `with` hands the targets back.  On entry the stream waits for the device's
+    _acc_fence if there is anything to add into, and the targets are recorded on it (they may have
+    been allocated on another view's stream); on a clean exit the launch made inside becomes the new
+    fence.  targets None: in-place accumulation was not attempted -- nothing is waited for or
+    recorded.  (A class, not a generator: this sits on every backward's host path.)"""
+    __slots__ = ("dev", "targets", "stream")
+
+    def __init__(self, dev, targets):
+        self.dev, self.targets = dev, targets
+
+    def __enter__(self):
+        if self.targets is not None:
+            self.stream = torch.cuda.current_stream(self.dev)
+            fence = _acc_fence.get(self.dev)
+            if self.targets and fence is not None:
+                self.stream.wait_event(fence)
+            for g in self.targets.values():
+                g.record_stream(self.stream)
+        return self.targets
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.targets is not None and exc_type is None:
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+            _acc_fence[self.dev] = ev
+
+
+def _accumulation(dev, inputs):
+    """accumulate= of one rasterizer backward with its ordering (_Fenced): the existing .grad of every
+    input of `inputs` (_named_inputs) that may be added into -- an absent input (None or empty, as dc
+    mostly is) has no target.  inputs None: no in-place accumulation (accumulate=None)."""
+    return _Fenced(dev, None if inputs is None else {
+        k: g for k, g in ((k, _accumulation_target(t)) for k, t in inputs.items()) if g is not None})
+
+
+def _autograd_order(grads):
+    """The binding's gradient tuple (8 entries, 9 with dL_ddc) in the order of the autograd functions'
+    inputs: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+    raster_settings (None), dc."""
+    g2d, g_col, g_op, g_m3, g_cov, *g_dc, g_sh, g_sc, g_rot = grads
+    return (g_m3, g2d, g_sh, g_col, g_op, g_sc, g_rot, g_cov, None, g_dc[0] if g_dc else None)
+
+
 class _DeferredBatch:
     """Views rendered inside deferred_backward: their render backward has run, their
     BACKWARD::preprocess waits for flush()."""
@@ -166,51 +217,37 @@ class _DeferredBatch:
             # out of the caching allocator's reuse on their own streams until it has run
             for t in (v["geom"], v["binning"], v["radii"]):
                 t.record_stream(stream)
-        inputs = {"means3D": c_m3, "dc": c_dc, "sh": c_sh, "opacities": c_op, "scales": c_sc, "rotations": c_rot,
-                  "cov3D_precomp": c_cov, "colors_precomp": c_col}
+        inputs = _named_inputs(c_m3, c_dc, c_sh, c_op, c_sc, c_rot, c_cov, c_col)
         on_chunk, done = _chunk_hook({k for k, t in inputs.items()
                                       if t is not None and t.numel() and t.requires_grad})
-        try:
-            # under a chunk hook (overlapped all-reduce) the gradients go into FRESH buffers, which the
-            # hook reduces, and reach an existing .grad by autograd's add below: adding into a .grad
-            # that already holds reduced gradients (an earlier launch group, a late view) and then
-            # reducing it again would multiply those by the world size
-            accumulate = {} if on_chunk is not None else {
-                k: g for k, g in ((k, _accumulation_target(t)) for k, t in inputs.items()) if g is not None}
-            if "dc" in accumulate and (dc is None or dc.numel() == 0):
-                del accumulate["dc"]
-            fence = _acc_fence.get(dev)
-            if accumulate and fence is not None:
-                stream.wait_event(fence)
-            for g in accumulate.values():
-                g.record_stream(stream)
-            grads = _C.rasterize_gaussians_preprocess_backward_views(
-                means3D, [v["radii"] for v in views], colors_precomp, opacities, scales, rotations,
-                s0.scale_modifier, cov3Ds_precomp, [v["settings"].viewmatrix for v in views],
-                [v["settings"].projmatrix for v in views], [v["settings"].tanfovx for v in views],
-                [v["settings"].tanfovy for v in views], s0.image_height, s0.image_width, sh, s0.sh_degree,
-                [v["settings"].campos for v in views], [v["geom"] for v in views], [v["num_rendered"] for v in views],
-                [v["binning"] for v in views], any(v["has_inv"] for v in views), s0.antialiasing, s0.debug, dc=dc,
-                accumulate=accumulate, on_chunk=on_chunk)
-        finally:
-            if done is not None:
-                done()
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        _acc_fence[dev] = ev
-        if len(grads) == 9:
-            g2d, g_col, g_op, g_m3, g_cov, g_dc, g_sh, g_sc, g_rot = grads
-        else:
-            g2d, g_col, g_op, g_m3, g_cov, g_sh, g_sc, g_rot = grads
-            g_dc = None
+        # under a chunk hook (overlapped all-reduce) the gradients go into FRESH buffers, which the
+        # hook reduces, and reach an existing .grad by autograd's add below: adding into a .grad
+        # that already holds reduced gradients (an earlier launch group, a late view) and then
+        # reducing it again would multiply those by the world size.  The launch is the device's new
+        # fence either way.
+        with _accumulation(dev, inputs if on_chunk is None else {}) as accumulate:
+            try:
+                grads = _C.rasterize_gaussians_preprocess_backward_views(
+                    means3D, [v["radii"] for v in views], colors_precomp, opacities, scales, rotations,
+                    s0.scale_modifier, cov3Ds_precomp, [v["settings"].viewmatrix for v in views],
+                    [v["settings"].projmatrix for v in views], [v["settings"].tanfovx for v in views],
+                    [v["settings"].tanfovy for v in views], s0.image_height, s0.image_width, sh, s0.sh_degree,
+                    [v["settings"].campos for v in views], [v["geom"] for v in views],
+                    [v["num_rendered"] for v in views], [v["binning"] for v in views],
+                    any(v["has_inv"] for v in views), s0.antialiasing, s0.debug, dc=dc, accumulate=accumulate,
+                    on_chunk=on_chunk)
+            finally:
+                if done is not None:
+                    done()
+        gs = _autograd_order(grads)
         # A leaf without a .grad (and without hooks) takes its gradient buffer as .grad, as autograd's
         # AccumulateGrad would (the parameter gradients stay views of ONE buffer: multiview's
         # in-place all-reduce); the rest goes through autograd: activations (exp, sigmoid,
         # normalize, cat) between the parameters and the rasterizer inputs, leaves with hooks.
         tensors, gts = [], []
-        pairs = [(c_m3, g_m3), (c_sh, g_sh), (c_col, g_col), (c_op, g_op), (c_sc, g_sc), (c_rot, g_rot),
-                 (c_cov, g_cov), (c_dc, g_dc)]
-        pairs += [(v["means2D"], g2d[j]) for j, v in enumerate(views)]
+        pairs = [(c_m3, gs[0]), (c_sh, gs[2]), (c_col, gs[3]), (c_op, gs[4]), (c_sc, gs[5]), (c_rot, gs[6]),
+                 (c_cov, gs[7]), (c_dc, gs[9])]
+        pairs += [(v["means2D"], gs[1][j]) for j, v in enumerate(views)]
         for t, g in pairs:
             if g is None or t is None or t.numel() == 0 or not t.requires_grad:
                 continue
@@ -301,11 +338,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.deferred = deferred  # (batch, the caller's inputs, the caller's means2D): deferred_backward
         # in-place accumulation (accumulate_grads_in_place): the inputs whose .grad the backward
         # may add into, kept by reference (leaves: the same tensors save_for_backward keeps)
-        ctx.acc_inputs = None
-        if getattr(_state, "accumulate", False):
-            ctx.acc_inputs = {"means3D": means3D, "dc": dc, "sh": sh, "opacities": opacities, "scales": scales,
-                              "rotations": rotations, "cov3D_precomp": cov3Ds_precomp,
-                              "colors_precomp": colors_precomp}
+        ctx.acc_inputs = _named_inputs(means3D, dc, sh, opacities, scales, rotations, cov3Ds_precomp,
+                                       colors_precomp) if getattr(_state, "accumulate", False) else None
         # outputs without a gradient (always radii; invdepth when the loss ignores it) arrive as None
         # instead of zero tensors that autograd would fill with a kernel of its own; backward treats
         # None as zero
@@ -345,37 +379,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                        "inputs": (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, sh, opacities, dc),
                        "caller_inputs": (i_col, i_m3, i_sc, i_rot, i_cov, i_sh, i_op, i_dc)})
             return (None,) * 11
-        accumulate = None
-        if ctx.acc_inputs is not None:
-            accumulate = {k: g for k, g in ((k, _accumulation_target(t)) for k, t in ctx.acc_inputs.items())
-                          if g is not None}
-            if "dc" in accumulate and (dc is None or dc.numel() == 0):
-                del accumulate["dc"]
-            dev = means3D.device
-            stream = torch.cuda.current_stream(dev)
-            fence = _acc_fence.get(dev)
-            if accumulate and fence is not None:
-                stream.wait_event(fence)
-            for g in accumulate.values():
-                g.record_stream(stream)  # may have been allocated on another view's stream
-        grads = _C.rasterize_gaussians_backward(
-            s.bg, means3D, radii, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
-            s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth, sh, s.sh_degree,
-            s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.antialiasing, s.debug, dc=dc,
-            accumulate=accumulate)
-        if ctx.acc_inputs is not None:
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            _acc_fence[dev] = ev
-        if len(grads) == 9:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_dc, grad_sh,
-             grad_scales, grad_rotations) = grads
-        else:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = grads
-            grad_dc = None
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, grad_dc, None)
+        with _accumulation(means3D.device, ctx.acc_inputs) as accumulate:
+            grads = _C.rasterize_gaussians_backward(
+                s.bg, means3D, radii, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
+                s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth, sh, s.sh_degree,
+                s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.antialiasing, s.debug, dc=dc,
+                accumulate=accumulate)
+        return _autograd_order(grads) + (None,)
 
 
 def _camera_guard(keyword):
@@ -482,21 +492,10 @@ class _FusedActivations(torch.autograd.Function):
                 dst[j] = out[j] = torch.empty(shapes[j], dtype=torch.float32, device=g.device)
         if all(g is None for g in gin):
             return None, None, None
-        dev = rotation.device
-        if ctx.acc_inputs is not None:
-            stream = torch.cuda.current_stream(dev)
-            fence = _acc_fence.get(dev)
-            if mask and fence is not None:
-                stream.wait_event(fence)
-            for j in range(3):
-                if mask >> j & 1:
-                    dst[j].record_stream(stream)  # may have been allocated on another view's stream
-        _C.activate_backward(scales, rotation, opacities, gin[0], gin[1], gin[2], dst[0], dst[1], dst[2],
-                             accumulate_mask=mask)
-        if ctx.acc_inputs is not None:
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            _acc_fence[dev] = ev
+        targets = None if ctx.acc_inputs is None else {j: dst[j] for j in range(3) if mask >> j & 1}
+        with _Fenced(rotation.device, targets):
+            _C.activate_backward(scales, rotation, opacities, gin[0], gin[1], gin[2], dst[0], dst[1], dst[2],
+                                 accumulate_mask=mask)
         return out[0], out[1], out[2]
 
 
@@ -519,33 +518,11 @@ class GaussianRasterizer(nn.Module):
         that replace the settings' three for this call and take part in autograd (pose refinement:
         multiview.pose_camera); those that require grad receive dL/dviewmatrix, dL/dprojmatrix and
         dL/dcampos, everything else is what the call without ``camera`` gives."""
-        s = self.raster_settings
-        if (shs is None) == (colors_precomp is None) or (dc is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        absent = torch.Tensor([])
+        args = _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
         if camera is not None:
             viewmatrix, projmatrix, campos = camera
-            return rasterize_gaussians_camera(
-                means3D, means2D,
-                absent if shs is None else shs,
-                absent if colors_precomp is None else colors_precomp,
-                opacities,
-                absent if scales is None else scales,
-                absent if rotations is None else rotations,
-                absent if cov3D_precomp is None else cov3D_precomp,
-                s, dc, viewmatrix, projmatrix, campos)
-        return rasterize_gaussians(
-            means3D, means2D,
-            absent if shs is None else shs,
-            absent if colors_precomp is None else colors_precomp,
-            opacities,
-            absent if scales is None else scales,
-            absent if rotations is None else rotations,
-            absent if cov3D_precomp is None else cov3D_precomp,
-            s, dc)
+            return rasterize_gaussians_camera(*args, self.raster_settings, dc, viewmatrix, projmatrix, campos)
+        return rasterize_gaussians(*args, self.raster_settings, dc)
 
 
 def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, dc):
@@ -555,6 +532,17 @@ def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, dc):
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
             ((scales is not None or rotations is not None) and cov3D_precomp is not None):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+
+
+def _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc):
+    """A rasterizer module's inputs, checked (_check_inputs), in the order rasterize_gaussians and
+    rasterize_views take them: means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+    cov3Ds_precomp -- an absent optional one as the reference's empty tensor."""
+    _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
+    absent = torch.Tensor([])
+    sh, colors_precomp, scales, rotations, cov3D_precomp = (
+        absent if t is None else t for t in (shs, colors_precomp, scales, rotations, cov3D_precomp))
+    return means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp
 
 
 def rasterize_views(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -599,11 +587,8 @@ class _RasterizeViews(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, dc,
                               *[t for st in state for t in st[1:]])
-        ctx.acc_inputs = None
-        if getattr(_state, "accumulate", False):
-            ctx.acc_inputs = {"means3D": means3D, "dc": dc, "sh": sh, "opacities": opacities, "scales": scales,
-                              "rotations": rotations, "cov3D_precomp": cov3Ds_precomp,
-                              "colors_precomp": colors_precomp}
+        ctx.acc_inputs = _named_inputs(means3D, dc, sh, opacities, scales, rotations, cov3Ds_precomp,
+                                       colors_precomp) if getattr(_state, "accumulate", False) else None
         return colors, radii, invdepths
 
     @staticmethod
@@ -621,44 +606,20 @@ class _RasterizeViews(torch.autograd.Function):
         names = {0: "means3D", 2: "sh", 3: "colors_precomp", 4: "opacities", 5: "scales", 6: "rotations",
                  7: "cov3D_precomp", 9: "dc"}
         on_chunk, done = _chunk_hook({n for i, n in names.items() if ctx.needs_input_grad[i]})
-        accumulate = None
         # no in-place accumulation under a chunk hook: the hook reduces what the kernel writes, and an
         # existing .grad may already hold reduced gradients (see _DeferredBatch._launch)
-        if ctx.acc_inputs is not None and on_chunk is None:
-            accumulate = {k: g for k, g in ((k, _accumulation_target(t)) for k, t in ctx.acc_inputs.items())
-                          if g is not None}
-            if "dc" in accumulate and (dc is None or dc.numel() == 0):
-                del accumulate["dc"]
-            dev = means3D.device
-            stream = torch.cuda.current_stream(dev)
-            fence = _acc_fence.get(dev)
-            if accumulate and fence is not None:
-                stream.wait_event(fence)
-            for g in accumulate.values():
-                g.record_stream(stream)
-        try:
-            grads = _C.rasterize_gaussians_backward_views(
-                s0.bg, means3D, [radii[v] for v in range(V)], colors_precomp, opacities, scales, rotations,
-                s0.scale_modifier, cov3Ds_precomp, [s.viewmatrix for s in ss], [s.projmatrix for s in ss],
-                [s.tanfovx for s in ss], [s.tanfovy for s in ss], grad_colors, grad_invdepths, sh, s0.sh_degree,
-                [s.campos for s in ss], bufs[0::3], ctx.num_rendered, bufs[1::3], bufs[2::3], s0.antialiasing,
-                s0.debug, dc=dc, accumulate=accumulate, on_chunk=on_chunk)
-        finally:
-            if done is not None:
-                done()
-        if accumulate is not None:
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            _acc_fence[dev] = ev
-        if len(grads) == 9:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_dc, grad_sh,
-             grad_scales, grad_rotations) = grads
-        else:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = grads
-            grad_dc = None
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
-                grad_rotations, grad_cov3Ds_precomp, None, grad_dc)
+        with _accumulation(means3D.device, ctx.acc_inputs if on_chunk is None else None) as accumulate:
+            try:
+                grads = _C.rasterize_gaussians_backward_views(
+                    s0.bg, means3D, [radii[v] for v in range(V)], colors_precomp, opacities, scales, rotations,
+                    s0.scale_modifier, cov3Ds_precomp, [s.viewmatrix for s in ss], [s.projmatrix for s in ss],
+                    [s.tanfovx for s in ss], [s.tanfovy for s in ss], grad_colors, grad_invdepths, sh, s0.sh_degree,
+                    [s.campos for s in ss], bufs[0::3], ctx.num_rendered, bufs[1::3], bufs[2::3], s0.antialiasing,
+                    s0.debug, dc=dc, accumulate=accumulate, on_chunk=on_chunk)
+            finally:
+                if done is not None:
+                    done()
+        return _autograd_order(grads)
 
 
 def rasterize_views_camera(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -731,8 +692,7 @@ class MultiViewRasterizer(nn.Module):
         projmatrices (V,4,4), campos (V,3)) or a list of V (viewmatrix, projmatrix, campos) triples;
         they replace the settings' for this call and take part in autograd
         (GaussianRasterizer.forward's ``camera``, per view)."""
-        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
-        absent = torch.Tensor([])
+        args = _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
         if cameras is not None:
             if len(cameras) == 3 and all(isinstance(t, torch.Tensor) and t.dim() >= 2 for t in cameras):
                 viewmatrices, projmatrices, campos = cameras
@@ -740,24 +700,8 @@ class MultiViewRasterizer(nn.Module):
                 if len(cameras) != len(self.raster_settings):
                     raise RuntimeError(f"cameras=: {len(self.raster_settings)} views, got {len(cameras)} cameras")
                 viewmatrices, projmatrices, campos = (torch.stack([c[k] for c in cameras]) for k in range(3))
-            return rasterize_views_camera(
-                means3D, means2D,
-                absent if shs is None else shs,
-                absent if colors_precomp is None else colors_precomp,
-                opacities,
-                absent if scales is None else scales,
-                absent if rotations is None else rotations,
-                absent if cov3D_precomp is None else cov3D_precomp,
-                self.raster_settings, dc, viewmatrices, projmatrices, campos)
-        return rasterize_views(
-            means3D, means2D,
-            absent if shs is None else shs,
-            absent if colors_precomp is None else colors_precomp,
-            opacities,
-            absent if scales is None else scales,
-            absent if rotations is None else rotations,
-            absent if cov3D_precomp is None else cov3D_precomp,
-            self.raster_settings, dc)
+            return rasterize_views_camera(*args, self.raster_settings, dc, viewmatrices, projmatrices, campos)
+        return rasterize_views(*args, self.raster_settings, dc)
 
 
 class SparseGaussianAdam(torch.optim.Adam):

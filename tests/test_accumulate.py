@@ -98,6 +98,28 @@ def test_accumulate_argument_checks():
     plain = dgr._C.rasterize_gaussians_backward(*args)
     assert out[3] is None
     torch.testing.assert_close(dst, plain[3] + 1.0, rtol=0, atol=0)
+    # the batched backward (V = 2 views of the same Gaussians) validates accumulate= the same way
+    import synthetic
+    ss = [s, _settings(case, synthetic.Camera(32, 32, view=1))]
+    st = [(L, radii, geom, binning, img)]
+    L1, _, radii1, geom1, binning1, img1, _ = dgr._C.rasterize_gaussians(
+        s.bg, sc["means3D"], e, sc["opacities"], sc["scales"], sc["rotations"], 1.0, e, ss[1].viewmatrix,
+        ss[1].projmatrix, ss[1].tanfovx, ss[1].tanfovy, 32, 32, sc["shs"], 3, ss[1].campos, False, False, False)
+    st.append((L1, radii1, geom1, binning1, img1))
+    gc = case["grad_color"].to(DEV)
+    vargs = (s.bg, sc["means3D"], [v[1] for v in st], e, sc["opacities"], sc["scales"], sc["rotations"], 1.0, e,
+             [x.viewmatrix for x in ss], [x.projmatrix for x in ss], [x.tanfovx for x in ss], [x.tanfovy for x in ss],
+             torch.stack([gc, gc]), None, sc["shs"], 3, [x.campos for x in ss], [v[2] for v in st],
+             [v[0] for v in st], [v[3] for v in st], [v[4] for v in st], False, False)
+    with pytest.raises(RuntimeError, match="accumulate"):
+        dgr._C.rasterize_gaussians_backward_views(*vargs, accumulate={"means3D": torch.zeros(5, device=DEV)})
+    with pytest.raises(RuntimeError, match="unknown"):
+        dgr._C.rasterize_gaussians_backward_views(*vargs, accumulate={"bogus": torch.zeros(600, device=DEV)})
+    # a dc target without dc: refused by both
+    with pytest.raises(RuntimeError):
+        dgr._C.rasterize_gaussians_backward(*args, accumulate={"dc": torch.zeros(600, device=DEV)})
+    with pytest.raises(RuntimeError):
+        dgr._C.rasterize_gaussians_backward_views(*vargs, accumulate={"dc": torch.zeros(600, device=DEV)})
 
 
 def test_views_on_two_streams_match_one_stream():

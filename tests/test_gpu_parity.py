@@ -321,6 +321,14 @@ def test_empty_and_all_culled():
     color, radii, inv = rast(means3D=z, means2D=z, opacities=torch.zeros((0, 1), device=DEV),
                              shs=torch.zeros((0, 16, 3), device=DEV), scales=z, rotations=torch.zeros((0, 4), device=DEV))
     assert color.shape == (3, case["H"], case["W"]) and float(color.abs().sum()) == 0.0 and radii.numel() == 0
+    # the same P = 0 inputs through a 2-view batch.  (No backward of P = 0 here: the binding takes M
+    # from the rows of `shs`, so without rows dL_dsh comes back as (0, 0, 3) and autograd refuses it
+    # for the (0, 16, 3) input -- in the single view and in the batch alike.)
+    colors, radii, invs = dgr.MultiViewRasterizer([s, s])(
+        means3D=z, means2D=torch.zeros((2, 0, 3), device=DEV), opacities=torch.zeros((0, 1), device=DEV),
+        shs=torch.zeros((0, 16, 3), device=DEV), scales=z, rotations=torch.zeros((0, 4), device=DEV))
+    assert colors.shape == (2, 3, case["H"], case["W"]) and float(colors.abs().sum()) == 0.0
+    assert radii.shape == (2, 0) and invs.shape == (2, 1, case["H"], case["W"]) and float(invs.abs().sum()) == 0.0
     # every point behind the camera: nothing rendered, image = background
     sc = {k: v.to(DEV) for k, v in case["scene"].items()}
     cam_c = case["cam"].camera_center.to(DEV)
