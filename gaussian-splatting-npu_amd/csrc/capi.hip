@@ -224,7 +224,7 @@ struct Camera {
     const float *view, *proj, *campos;
     float tan_fovx, tan_fovy;
 };
-// One view's state buffers and outputs (radii null: the GeometryState's own)
+// One view's state buffers and outputs (radii null: the GeometryState's own; the backward only reads them)
 struct ViewState {
     char *geometry, *image, *binning;
     size_t binning_capacity;
@@ -905,9 +905,9 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
     return forward_prealloc(sc, V, cam, vs, background, opt, caller, caller, debug, num_rendered, rendered);
 }
 
-// render_bwd's arguments for one view (P, R > 0)
+// render_bwd's arguments for one view (P, R > 0), and the job of its backward tile order
 static RenderBwdArgs render_bwd_args(const Scene& sc, const ViewState& vs, int R, const float* background,
-                                     const float* dL_dpix, const float* dL_invdepths)
+                                     const float* dL_dpix, const float* dL_invdepths, OrderJob* order)
 {
     const int width = sc.width, height = sc.height;
     char *gb = vs.geometry, *ib = vs.image, *bb = vs.binning;
@@ -934,61 +934,98 @@ static RenderBwdArgs render_bwd_args(const Scene& sc, const ViewState& vs, int R
     r.hit = at<uint8_t>(bb, b.off[BIN_HIT]);
     r.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
     r.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
+    *order = {nullptr, r.tile_work, at<uint32_t>(ib, im.off[IMG_TILE_ORDER])};
     return r;
 }
 
-// BACKWARD::render of one view (rasterizer_impl.cu:399-418; P, R > 0): the backward's tile order
-// (longest n_contrib first), then the per-(tile, Gaussian) gradient records
-static int backward_render_impl(const Scene& sc, const ViewState& vs, int R, const float* background,
-                                const float* dL_dpix, const float* dL_invdepths, bool debug, hipStream_t s)
+// The backward of V >= 1 views of the same Gaussians, like the forward, exists once: backward_render,
+// then backward_preprocess.  What the entry points differ in they pass in (BackwardOptions).
+// The parameter gradients BACKWARD::preprocess writes (summed over the views) and their GSR_ACC_* bits
+struct ParamGrads {
+    float *dL_dcolor, *dL_dopacity, *dL_dmean3D, *dL_dcov3D, *dL_ddc, *dL_dsh, *dL_dscale, *dL_drot;
+    unsigned accumulate;
+};
+
+// What every backward that reads the Gaussians' parameters checks of them (no HIP call).
+// g: the gradients it writes; null for the camera gradient, which writes none
+static int backward_scene_check(const Scene& sc, const ParamGrads* g)
 {
-    const ImageLayout im = image_layout(sc.width, sc.height);
-    const RenderBwdArgs r = render_bwd_args(sc, vs, R, background, dL_dpix, dL_invdepths);
-    {
-        ProfScope ps_(PK_TILE_ORDER, s);
-        HIP_TRY(launch_tile_order(nullptr, r.tile_work, r.T, at<uint32_t>(vs.image, im.off[IMG_TILE_ORDER]), s));
+    if (g && (g->accumulate & ~(unsigned)GSR_ACC_ALL)) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
+    if (sc.P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
+    if (g && sc.dc && !g->dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
+    if (sc.dc && sc.colors_precomp)
+        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
+    if (sc.dc && sc.M > 0 && (!sc.shs || (g && !g->dL_dsh)))
+        return fail(GSR_ERR_INVALID,
+                    g ? "dc given with M > 0 but shs/dL_dsh NULL" : "dc given with M > 0 but shs NULL");
+    if (sc.P > 0 && (!sc.means3D || !sc.opacities || (!sc.cov3D_precomp && (!sc.scales || !sc.rotations))))
+        return fail(GSR_ERR_INVALID, "null parameter array");
+    return GSR_OK;
+}
+
+// The ABI's parallel per-view arrays (non-null: the entry point checks that ahead of its P == 0 return;
+// their elements are read only here, after it) as ViewState[] and, with cameras (ca), Camera[], under the
+// checks every batched backward applies: R[v] >= 0, no null camera, and with P > 0 no null state buffer a
+// kernel would read -- geometry, image (null: no BACKWARD::render in this call), binning when R[v] > 0.
+struct CameraArrays { const float *const *view, *const *proj, *const *campos, *tan_fovx, *tan_fovy; };
+static int unpack_views(int V, int P, const int* R, const CameraArrays* ca, char* const* geometry, char* const* image,
+                        char* const* binning, const int* const* radii, Camera* cam, ViewState* vs)
+{
+    for (int v = 0; v < V; v++) {
+        if (R[v] < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
+        if (ca && (!ca->view[v] || !ca->proj[v] || !ca->campos[v])) return fail(GSR_ERR_INVALID, "null camera");
+        if (P > 0 && (!geometry[v] || (image && !image[v]) || (R[v] > 0 && !binning[v])))
+            return fail(GSR_ERR_ALLOC, "null state buffer");
+        if (ca) cam[v] = {ca->view[v], ca->proj[v], ca->campos[v], ca->tan_fovx[v], ca->tan_fovy[v]};
+        vs[v] = {geometry[v], image ? image[v] : nullptr, binning[v], 0, nullptr, nullptr,
+                 radii ? const_cast<int*>(radii[v]) : nullptr};  // (the backward only reads radii)
     }
-    {
+    return GSR_OK;
+}
+
+// BACKWARD::render (rasterizer_impl.cu:399-418) of n views (arguments checked, P > 0; a view with R[v] == 0
+// has no instances, so no records to write, and is skipped): every view's backward tile order (longest
+// n_contrib first) in one launch, then their per-(tile, Gaussian) gradient records in one launch
+static int backward_render(const Scene& sc, int n, const ViewState* vs, const int* R, const float* const* dL_dpix,
+                           const float* const* dL_invdepths, const float* background, bool debug, hipStream_t s)
+{
+    OrderJob oj[MAX_VIEWS];
+    RenderBwdArgs ra[MAX_VIEWS];
+    int nr = 0;
+    for (int v = 0; v < n; v++) {
+        if (R[v] == 0) continue;
+        const float* dL_inv = dL_invdepths ? dL_invdepths[v] : nullptr;
+        ra[nr] = render_bwd_args(sc, vs[v], R[v], background, dL_dpix[v], dL_inv, &oj[nr]);
+        nr++;
+    }
+    if (nr) {
+        ProfScope ps_(PK_TILE_ORDER, s);
+        HIP_TRY(launch_tile_order_batch(oj, nr, ra[0].T, s));
+    }
+    if (nr) {
         ProfScope ps_(PK_RENDER_BWD, s);  // valid[] was cleared by the forward's tile sort
-        HIP_TRY(launch_render_bwd(r, r.T, s));
+        HIP_TRY(launch_render_bwd_batch(ra, nr, ra[0].T, s));
     }
     DEBUG_SYNC(s);
     return GSR_OK;
 }
 
-// What the single-view and the batched preprocess_bwd share: the argument checks, the per-Gaussian
-// parameters and the gradient outputs (the single view's extras -- radii, dL_dconic, dL_dinvdepth --
-// stay null here).
-static int preprocess_bwd_shared(PreprocessBwdArgs& p, const Scene& sc, bool has_invdepth, float* dL_dcolor,
-                                 float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
-                                 float* dL_dsh, float* dL_dscale, float* dL_drot, unsigned accumulate)
+// The parameters and flags that preprocess_bwd and the camera gradient read from the Scene (no outputs)
+static void preprocess_bwd_params(PreprocessBwdArgs& p, const Scene& sc, bool has_invdepth)
 {
-    if (accumulate & ~(unsigned)GSR_ACC_ALL) return fail(GSR_ERR_INVALID, "unknown accumulate bits");
-    if (sc.dc && !dL_ddc) return fail(GSR_ERR_INVALID, "dc given without dL_ddc");
-    if (sc.dc && sc.colors_precomp)
-        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (sc.dc && sc.M > 0 && (!sc.shs || !dL_dsh))
-        return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs/dL_dsh NULL");
     p.P = sc.P; p.D = sc.D; p.M = sc.dc ? sc.M + 1 : sc.M;
-    p.means3D = sc.means3D; p.radii = nullptr; p.shs = sc.shs; p.dc = sc.dc; p.dL_ddc = sc.dc ? dL_ddc : nullptr;
+    p.means3D = sc.means3D; p.radii = nullptr; p.shs = sc.shs; p.dc = sc.dc;
     p.opacities = sc.opacities; p.scales = sc.scales; p.rotations = sc.rotations;
     p.scale_modifier = sc.scale_modifier;
     p.cov3D_precomp = sc.cov3D_precomp;
     p.antialiasing = sc.antialiasing;
     p.has_invdepth = has_invdepth;
     p.W = sc.width; p.H = sc.height;
-    p.dL_dconic = nullptr; p.dL_dinvdepth = nullptr;
-    p.dL_dopacity = dL_dopacity; p.dL_dcolor = dL_dcolor;
-    p.dL_dmean3D = dL_dmean3D; p.dL_dcov3D = dL_dcov3D; p.dL_dsh = (sc.shs && sc.M > 0) ? dL_dsh : nullptr;
-    p.dL_dscale = dL_dscale; p.dL_drot = dL_drot;
-    p.acc = accumulate;
-    return GSR_OK;
 }
 
 // One view's part of preprocess_bwd's arguments (L: its num_rendered; vs.binning may be null when
-// L == 0; radii: what the forward wrote, null for the GeometryState's own)
-static BwdView bwd_view(const Scene& sc, const Camera& cam, const ViewState& vs, int L, const int* radii,
-                        float* dL_dmean2D)
+// L == 0; vs.radii: what the forward wrote, null for the GeometryState's own)
+static BwdView bwd_view(const Scene& sc, const Camera& cam, const ViewState& vs, int L, float* dL_dmean2D)
 {
     char *gb = vs.geometry, *bb = vs.binning;
     const GeomLayout g = geom_layout(sc.P);
@@ -998,7 +1035,7 @@ static BwdView bwd_view(const Scene& sc, const Camera& cam, const ViewState& vs,
     bv.focal_y = sc.height / (2.0f * cam.tan_fovy);
     bv.focal_x = sc.width / (2.0f * cam.tan_fovx);
     bv.tan_fovx = cam.tan_fovx; bv.tan_fovy = cam.tan_fovy;
-    bv.radii = radii ? radii : at<int>(gb, g.off[GEOM_RADII]);
+    bv.radii = vs.radii ? vs.radii : at<int>(gb, g.off[GEOM_RADII]);
     bv.conic_opacity = at<float4>(gb, g.off[GEOM_CONIC_OPACITY]);
     bv.clamped = at<uint8_t>(gb, g.off[GEOM_CLAMPED]);
     bv.emit_start = at<uint32_t>(gb, g.off[GEOM_EMIT_START]);
@@ -1008,6 +1045,47 @@ static BwdView bwd_view(const Scene& sc, const Camera& cam, const ViewState& vs,
     bv.rec_mask = at<uint32_t>(gb, g.off[GEOM_REC_MASK]);
     bv.dL_dmean2D = dL_dmean2D;
     return bv;
+}
+
+// The single view keeps its own launcher: one lane per Gaussian, gated on the caller's radii, which
+// also writes the reference glue's other render-pass gradients.  (The V == 1 case of the batched one is
+// another kernel instantiation, two lanes per Gaussian, whose sums round differently.)
+enum PreprocessBwdLauncher { PREPROCESS_BWD_SINGLE, PREPROCESS_BWD_VIEWS };
+struct BackwardOptions {
+    PreprocessBwdLauncher preprocess;  // launch_preprocess_bwd_single (V == 1, the whole range) or _views
+    int g_begin, g_end;                // the Gaussians [g_begin, g_end) whose gradient rows are written
+    float *dL_dconic, *dL_dinvdepth;   // the single view's extras (null for batches)
+};
+
+// BACKWARD::preprocess (rasterizer_impl.cu:423-449) of V views (arguments checked, P > 0) with the gather of
+// their gradient records: one pass over the Gaussians of the range.  has_invdepth: some view's records
+// carry an inverse-depth gradient (a view rendered without one has zero invdepth fields in its records:
+// subtracting their zero term leaves its gradients bit-identical)
+static int backward_preprocess(const Scene& sc, int V, const Camera* cam, const ViewState* vs, const int* R,
+                               bool has_invdepth, float* const* dL_dmean2D, const ParamGrads& g,
+                               const BackwardOptions& opt, bool debug, hipStream_t s)
+{
+    PreprocessBwdViewsArgs A;
+    PreprocessBwdArgs& p = A.a;
+    preprocess_bwd_params(p, sc, has_invdepth);
+    p.dL_dconic = opt.dL_dconic; p.dL_dinvdepth = opt.dL_dinvdepth;
+    p.dL_dopacity = g.dL_dopacity; p.dL_dcolor = g.dL_dcolor;
+    p.dL_dmean3D = g.dL_dmean3D; p.dL_dcov3D = g.dL_dcov3D;
+    p.dL_ddc = sc.dc ? g.dL_ddc : nullptr; p.dL_dsh = (sc.shs && sc.M > 0) ? g.dL_dsh : nullptr;
+    p.dL_dscale = g.dL_dscale; p.dL_drot = g.dL_drot;
+    p.acc = g.accumulate;
+    A.V = V;
+    A.g_begin = opt.g_begin;
+    A.g_end = opt.g_end;
+    for (int v = 0; v < V; v++) A.v[v] = bwd_view(sc, cam[v], vs[v], R[v], dL_dmean2D[v]);
+    const bool single = opt.preprocess == PREPROCESS_BWD_SINGLE;
+    if (single) p.radii = A.v[0].radii;  // (the one-lane kernel gates on them)
+    {
+        ProfScope ps_(PK_PREPROCESS_BWD, s);
+        HIP_TRY(single ? launch_preprocess_bwd_single(A, s) : launch_preprocess_bwd_views(A, s));
+    }
+    DEBUG_SYNC(s);
+    return GSR_OK;
 }
 
 int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int width, int height,
@@ -1024,36 +1102,24 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
     const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
                       cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
     const Camera cam = {viewmatrix, projmatrix, campos, tan_fovx, tan_fovy};
-    const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, nullptr};
-    PreprocessBwdViewsArgs A;
-    int rc = preprocess_bwd_shared(A.a, sc, dL_invdepths != nullptr, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D,
-                                   dL_ddc, dL_dsh, dL_dscale, dL_drot, accumulate);
+    const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, const_cast<int*>(radii)};
+    const ParamGrads g = {dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                          accumulate};
+    int rc = backward_scene_check(sc, &g);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (P <= 0) return GSR_OK;
+    if (R < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
+    if (P == 0) return GSR_OK;
     if (R > 0 && !binning_buffer) return fail(GSR_ERR_ALLOC, "null binning buffer");
-    if ((dL_invdepths == nullptr) != (dL_dinvdepth == nullptr) && dL_dinvdepth == nullptr)
-        return fail(GSR_ERR_INVALID, "dL_dinvdepth must be given with dL_invdepths");
+    if (!geom_buffer || (R > 0 && !image_buffer)) return fail(GSR_ERR_ALLOC, "null state buffer");
+    if (R > 0 && !dL_dpix) return fail(GSR_ERR_INVALID, "null dL_dpix");
+    if (dL_invdepths && !dL_dinvdepth) return fail(GSR_ERR_INVALID, "dL_dinvdepth must be given with dL_invdepths");
+    hipStream_t s = (hipStream_t)stream;
     if (R > 0) {  // (no instances: no records to write)
-        rc = backward_render_impl(sc, vs, R, background, dL_dpix, dL_invdepths, debug, s);
+        rc = backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr, background, debug, s);
         if (rc) return rc;
     }
-    // BACKWARD::preprocess (rasterizer_impl.cu:423-449), with the per-Gaussian gather of the records:
-    // the batched kernel at one lane per Gaussian (launch_preprocess_bwd_single), which also writes the
-    // reference glue's other render-pass gradients
-    A.V = 1;
-    A.g_begin = 0;
-    A.g_end = P;
-    A.v[0] = bwd_view(sc, cam, vs, R, radii, dL_dmean2D);
-    A.a.radii = A.v[0].radii;
-    A.a.dL_dconic = dL_dconic;
-    A.a.dL_dinvdepth = dL_dinvdepth;
-    {
-        ProfScope ps_(PK_PREPROCESS_BWD, s);
-        HIP_TRY(launch_preprocess_bwd_single(A, s));
-    }
-    DEBUG_SYNC(s);
-    return GSR_OK;
+    const BackwardOptions opt = {PREPROCESS_BWD_SINGLE, 0, P, dL_dconic, dL_dinvdepth};
+    return backward_preprocess(sc, 1, &cam, &vs, &R, dL_invdepths != nullptr, &dL_dmean2D, g, opt, debug, s);
 }
 
 int gsr_backward_dc(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -1077,7 +1143,6 @@ int gsr_backward_render(int P, int R, const float* background, int width, int he
                         char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_invdepths,
                         bool debug, gsr_stream_t stream)
 {
-    hipStream_t s = (hipStream_t)stream;
     if (P < 0 || R < 0) return fail(GSR_ERR_INVALID, "P and R must be >= 0");
     if (P == 0 || R == 0) return GSR_OK;
     if (!geom_buffer || !image_buffer || !binning_buffer) return fail(GSR_ERR_ALLOC, "null state buffer");
@@ -1085,7 +1150,8 @@ int gsr_backward_render(int P, int R, const float* background, int width, int he
     Scene sc = {};
     sc.P = P; sc.width = width; sc.height = height;  // (all that BACKWARD::render reads)
     const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, nullptr};
-    return backward_render_impl(sc, vs, R, background, dL_dpix, dL_invdepths, debug, s);
+    return backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr, background, debug,
+                           (hipStream_t)stream);
 }
 
 int gsr_backward_preprocess_views(int V, int P, int D, int M, const int* R, int width, int height,
@@ -1125,34 +1191,23 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
     if (g_begin < 0 || g_end > P || g_begin > g_end) return fail(GSR_ERR_INVALID, "range outside [0, P)");
     const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
                       cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
-    PreprocessBwdViewsArgs A;
-    // a view rendered without an inverse-depth gradient has zero invdepth fields in its records:
-    // subtracting their (zero) term leaves its gradients bit-identical
-    const int rc = preprocess_bwd_shared(A.a, sc, has_invdepth, dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc,
-                                         dL_dsh, dL_dscale, dL_drot, accumulate);
+    const ParamGrads g = {dL_dcolor, dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                          accumulate};
+    int rc = backward_scene_check(sc, &g);
     if (rc) return rc;
     if (!R || !viewmatrices || !projmatrices || !campos || !tan_fovx || !tan_fovy || !geom_buffers ||
         !binning_buffers || !dL_dmean2D)
         return fail(GSR_ERR_INVALID, "null per-view array");
-    hipStream_t s = (hipStream_t)stream;
-    if (P <= 0) return GSR_OK;
-    A.V = V;
-    A.g_begin = g_begin;
-    A.g_end = g_end;
-    for (int v = 0; v < V; v++) {
-        if (!geom_buffers[v] || (R[v] > 0 && !binning_buffers[v])) return fail(GSR_ERR_ALLOC, "null state buffer");
+    if (P == 0) return GSR_OK;
+    const CameraArrays ca = {viewmatrices, projmatrices, campos, tan_fovx, tan_fovy};
+    Camera cam[MAX_VIEWS];
+    ViewState vs[MAX_VIEWS];
+    rc = unpack_views(V, P, R, &ca, geom_buffers, nullptr, binning_buffers, radii, cam, vs);
+    if (rc) return rc;
+    for (int v = 0; v < V; v++)
         if (!dL_dmean2D[v]) return fail(GSR_ERR_INVALID, "null per-view gradient");
-        const Camera cam = {viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v], tan_fovy[v]};
-        const ViewState vs = {geom_buffers[v], nullptr, binning_buffers[v], 0, nullptr, nullptr, nullptr};
-        A.v[v] = bwd_view(sc, cam, vs, R[v], radii ? radii[v] : nullptr, dL_dmean2D[v]);
-    }
-    // BACKWARD::preprocess (rasterizer_impl.cu:423-449) of the whole batch: one pass over the Gaussians
-    {
-        ProfScope ps_(PK_PREPROCESS_BWD, s);
-        HIP_TRY(launch_preprocess_bwd_views(A, s));
-    }
-    DEBUG_SYNC(s);
-    return GSR_OK;
+    const BackwardOptions opt = {PREPROCESS_BWD_VIEWS, g_begin, g_end, nullptr, nullptr};
+    return backward_preprocess(sc, V, cam, vs, R, has_invdepth, dL_dmean2D, g, opt, debug, (hipStream_t)stream);
 }
 
 size_t gsr_camera_grad_workspace_size(int V, int P) { return camera_bwd_workspace_bytes(V, P); }
@@ -1167,35 +1222,24 @@ int gsr_backward_camera_views(int V, int P, int D, int M, const int* R, int widt
                               float* dL_dprojmatrix, float* dL_dcampos, bool debug, gsr_stream_t stream)
 {
     if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
-    if (P < 0) return fail(GSR_ERR_INVALID, "P must be >= 0");
     if (!workspace || !dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
         return fail(GSR_ERR_INVALID, "null workspace or camera gradient");
-    if (dc && colors_precomp)
-        return fail(GSR_ERR_INVALID, "Please provide exactly one of either SHs or precomputed colors!");
-    if (dc && M > 0 && !shs) return fail(GSR_ERR_INVALID, "dc given with M > 0 but shs NULL");
+    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                      cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
+    int rc = backward_scene_check(sc, nullptr);
+    if (rc) return rc;
     if (!R || !viewmatrices || !projmatrices || !campos || !tan_fovx || !tan_fovy || !geom_buffers ||
         !binning_buffers)
         return fail(GSR_ERR_INVALID, "null per-view array");
-    if (P > 0 && (!means3D || !opacities || (!cov3D_precomp && (!scales || !rotations))))
-        return fail(GSR_ERR_INVALID, "null parameter array");
-    const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
-                      cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
+    const CameraArrays ca = {viewmatrices, projmatrices, campos, tan_fovx, tan_fovy};
+    Camera cam[MAX_VIEWS];
+    ViewState vs[MAX_VIEWS];
+    rc = unpack_views(V, P, R, &ca, geom_buffers, nullptr, binning_buffers, nullptr, cam, vs);
+    if (rc) return rc;
     CameraBwdArgs A = {};
-    PreprocessBwdArgs& p = A.a;  // the parameters and flags of preprocess_bwd_shared; no outputs
-    p.P = P; p.D = D; p.M = dc ? M + 1 : M;
-    p.means3D = means3D; p.shs = shs; p.dc = dc; p.opacities = opacities; p.scales = scales;
-    p.rotations = rotations; p.scale_modifier = scale_modifier; p.cov3D_precomp = cov3D_precomp;
-    p.antialiasing = antialiasing; p.has_invdepth = has_invdepth; p.W = width; p.H = height;
+    preprocess_bwd_params(A.a, sc, has_invdepth);  // (no gradient outputs)
     A.V = V;
-    for (int v = 0; v < V; v++) {
-        if (R[v] < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
-        if (!viewmatrices[v] || !projmatrices[v] || !campos[v]) return fail(GSR_ERR_INVALID, "null camera");
-        if (P > 0 && (!geom_buffers[v] || (R[v] > 0 && !binning_buffers[v])))
-            return fail(GSR_ERR_ALLOC, "null state buffer");
-        const Camera cam = {viewmatrices[v], projmatrices[v], campos[v], tan_fovx[v], tan_fovy[v]};
-        const ViewState vs = {geom_buffers[v], nullptr, binning_buffers[v], 0, nullptr, nullptr, nullptr};
-        if (P > 0) A.v[v] = bwd_view(sc, cam, vs, R[v], nullptr, nullptr);
-    }
+    for (int v = 0; v < V && P > 0; v++) A.v[v] = bwd_view(sc, cam[v], vs[v], R[v], nullptr);
     A.partial = reinterpret_cast<float*>(workspace);
     A.dL_dview = dL_dviewmatrix; A.dL_dproj = dL_dprojmatrix; A.dL_dcampos = dL_dcampos;
     hipStream_t s = (hipStream_t)stream;
@@ -1215,42 +1259,15 @@ int gsr_backward_render_views(int V, int P, const int* R, const float* backgroun
     if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
     if (!R || !geom_buffers || !binning_buffers || !image_buffers || !dL_dpix)
         return fail(GSR_ERR_INVALID, "null per-view array");
-    const bool has_inv = dL_invdepths != nullptr;
-    if (P <= 0) return GSR_OK;
-    // every view's backward tile order (longest n_contrib first) in one launch
-    OrderJob oj[MAX_VIEWS];
-    int no = 0;
-    const ImageLayout im = image_layout(width, height);
-    const int T = TileGrid(width, height).T;
-    for (int v = 0; v < V; v++) {
-        if (!image_buffers[v]) return fail(GSR_ERR_ALLOC, "null state buffer");
-        if (R[v] > 0)
-            oj[no++] = {nullptr, at<uint32_t>(image_buffers[v], im.off[IMG_TILE_WORK]),
-                        at<uint32_t>(image_buffers[v], im.off[IMG_TILE_ORDER])};
-    }
-    // BACKWARD::render of every view (its per-(tile, Gaussian) records), one launch per batch
+    if (P <= 0) return P < 0 ? fail(GSR_ERR_INVALID, "P must be >= 0") : GSR_OK;
     Scene sc = {};
     sc.P = P; sc.width = width; sc.height = height;  // (all that BACKWARD::render reads)
-    RenderBwdArgs ra[MAX_VIEWS];
-    int nr = 0;
-    for (int v = 0; v < V; v++) {
-        if (!dL_dpix[v] || (has_inv && !dL_invdepths[v])) return fail(GSR_ERR_INVALID, "null per-view gradient");
-        if (R[v] < 0) return fail(GSR_ERR_INVALID, "R must be >= 0");
-        if (R[v] == 0) continue;
-        if (!geom_buffers[v] || !binning_buffers[v]) return fail(GSR_ERR_ALLOC, "null state buffer");
-        const ViewState vs = {geom_buffers[v], image_buffers[v], binning_buffers[v], 0, nullptr, nullptr, nullptr};
-        ra[nr++] = render_bwd_args(sc, vs, R[v], background, dL_dpix[v], has_inv ? dL_invdepths[v] : nullptr);
-    }
-    if (no) {
-        ProfScope ps_(PK_TILE_ORDER, (hipStream_t)stream);
-        HIP_TRY(launch_tile_order_batch(oj, no, T, (hipStream_t)stream));
-    }
-    if (nr) {
-        ProfScope ps_(PK_RENDER_BWD, (hipStream_t)stream);  // valid[] was cleared by the forward
-        HIP_TRY(launch_render_bwd_batch(ra, nr, T, (hipStream_t)stream));
-    }
-    DEBUG_SYNC((hipStream_t)stream);
-    return GSR_OK;
+    ViewState vs[MAX_VIEWS];
+    const int rc = unpack_views(V, P, R, nullptr, geom_buffers, image_buffers, binning_buffers, nullptr, nullptr, vs);
+    if (rc) return rc;
+    for (int v = 0; v < V; v++)
+        if (!dL_dpix[v] || (dL_invdepths && !dL_invdepths[v])) return fail(GSR_ERR_INVALID, "null per-view gradient");
+    return backward_render(sc, V, vs, R, dL_dpix, dL_invdepths, background, debug, (hipStream_t)stream);
 }
 
 int gsr_backward_views(int V, int P, int D, int M, const int* R, const float* background, int width, int height,

@@ -148,7 +148,7 @@ struct BwdView {
 };
 struct PreprocessBwdViewsArgs {
     PreprocessBwdArgs a;
-    int V;  // 0: the single view of `a`
+    int V;  // views in v[] (1 for the single view, whose launcher also reads a.radii)
     int g_begin, g_end;  // the Gaussians [g_begin, g_end) of this launch (a chunk of [0, P))
     BwdView v[MAX_VIEWS];
 };
@@ -313,6 +313,8 @@ struct OrderJob {
     uint2* ranges_out;
     uint32_t grid_x, grid_y;
 };
+// Longest-first launch order of each view's T tiles: order[] = tiles by decreasing work, work = range
+// length (ranges, the forward) or work[] (the backward's per-tile largest n_contrib).
 // every job with ranges (the forward's order), every job with diff (the forward's, ranges written),
 // or every job with work (the backward's)
 hipError_t launch_tile_order_batch(const OrderJob* jobs, int V, int T, hipStream_t s);
@@ -336,10 +338,6 @@ hipError_t launch_debug_keys(int L, const uint32_t* sorted_tiles, const uint32_t
 hipError_t launch_debug_keys_from_ranges(int T, const uint2* ranges, const uint32_t* point_list, const uint32_t* dkeys,
                                          uint64_t* keys, hipStream_t s);
 
-// Longest-first launch order of the T tiles: order[] = tiles by decreasing work, work = range length
-// (ranges != null, the forward) or work[] (the backward's per-tile largest n_contrib).
-hipError_t launch_tile_order(const uint2* ranges, const uint32_t* work, int T, uint32_t* order, hipStream_t s);
-hipError_t launch_render_bwd(const RenderBwdArgs& a, int T, hipStream_t s);
 // V views of one image size in one launch per VIEW_BATCH views (grid.y = view); render_bwd: every
 // view with dL_invdepths, or none
 hipError_t launch_render_fwd_batch(const RenderFwdArgs* a, int V, int T, hipStream_t s);

@@ -988,12 +988,6 @@ hipError_t launch_tile_order_batch(const OrderJob* jobs, int V, int T, hipStream
     return hipSuccess;
 }
 
-hipError_t launch_tile_order(const uint2* ranges, const uint32_t* work, int T, uint32_t* order, hipStream_t s)
-{
-    const OrderJob j = {ranges, work, order};
-    return launch_tile_order_batch(&j, 1, T, s);
-}
-
 hipError_t launch_render_fwd_batch(const RenderFwdArgs* a, int V, int T, hipStream_t s)
 {
     if (T <= 0) return hipSuccess;
@@ -1030,7 +1024,5 @@ hipError_t launch_render_bwd_batch(const RenderBwdArgs* a, int V, int T, hipStre
     }
     return hipSuccess;
 }
-
-hipError_t launch_render_bwd(const RenderBwdArgs& a, int T, hipStream_t s) { return launch_render_bwd_batch(&a, 1, T, s); }
 
 }  // namespace gsr

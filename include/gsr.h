@@ -140,7 +140,14 @@ int gsr_forward_prealloc(char* geometry_buffer, char* image_buffer, char* binnin
  * backward.cu:163,420 do; a Gaussian with radius 0 gets zeros in EVERY output,
  * including the render-pass ones the reference would still report from its
  * render backward -- the two agree for radii produced by the forward (radius 0
- * <=> no tile <=> no record). */
+ * <=> no tile <=> no record).
+ * Argument checks (gsr_backward, gsr_backward_dc, gsr_backward_dc_acc alike): P < 0
+ * ("P must be >= 0") or R < 0 ("R must be >= 0") is GSR_ERR_INVALID; with P > 0, a
+ * NULL means3D or opacities, or a NULL scales or rotations without cov3D_precomp, is
+ * GSR_ERR_INVALID ("null parameter array"), a NULL geom_buffer, or with R > 0 a NULL
+ * image_buffer, is GSR_ERR_ALLOC ("null state buffer"; a NULL binning_buffer with
+ * R > 0: "null binning buffer"), and with R > 0 a NULL dL_dpix is GSR_ERR_INVALID
+ * ("null dL_dpix").  P == 0 returns GSR_OK without reading a buffer. */
 int gsr_backward(int P, int D, int M, int R,
                  const float* background,
                  int width, int height,
@@ -269,7 +276,17 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
  * view from that view's forward state (its tiles_touched, i.e. radius > 0 as the forward computed
  * it), where the reference gates on the radii passed in (backward.cu:163,420).  The two agree for
  * radii produced by the forward; a caller that edits radii between forward and backward has that
- * edit ignored here (the single-view gsr_backward* entry points do read radii). */
+ * edit ignored here (the single-view gsr_backward* entry points do read radii).
+ * Argument checks of the batched backward entry points (this one, its halves below and
+ * gsr_backward_camera_views): V outside [1, 16], P < 0 or a NULL per-view array is GSR_ERR_INVALID.
+ * This entry point and its halves return GSR_OK for P == 0 without reading an element of a per-view
+ * array, so the per-view checks that follow apply to them with P > 0 only; gsr_backward_camera_views
+ * has no such return (it writes its zeros for P == 0) and applies the first two for every P.
+ * Per view: R[v] < 0 ("R must be >= 0"), a NULL viewmatrices[v], projmatrices[v] or campos[v]
+ * ("null camera") and a NULL per-view gradient are GSR_ERR_INVALID; with P > 0 a NULL means3D or
+ * opacities, or a NULL scales or rotations without cov3D_precomp, is GSR_ERR_INVALID ("null parameter
+ * array"), and a NULL geom_buffers[v] or image_buffers[v] of any view, or a NULL binning_buffers[v]
+ * of a view with R[v] > 0, is GSR_ERR_ALLOC ("null state buffer"). */
 int gsr_backward_views(int V, int P, int D, int M, const int* R, const float* background, int width, int height,
                        const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
                        const float* opacities, const float* scales, float scale_modifier, const float* rotations,
