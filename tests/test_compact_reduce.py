@@ -24,8 +24,28 @@ def _rpw():
     return _C().union_rows_per_wave()
 
 
+def _large_sizes():
+    """union_offsets_kernel: 256 threads, thread t owns the per = ceil(nw / 256) waves from t per on.
+    256 waves (every thread one: the serial pass sees 256 partial sums), 257 waves (per = 2: threads
+    0..127 two waves, thread 128 the last wave of one row) and 770 waves less 19 rows (per = 4)."""
+    rpw = _rpw()
+    return [256 * rpw, 256 * rpw + 1, 770 * rpw - 19]
+
+
 def _plan_sizes():
-    return SIZES + [2 * _rpw() + 5, 5 * _rpw()]
+    return SIZES + [2 * _rpw() + 5, 5 * _rpw()] + _large_sizes()
+
+
+def _plan_bounds(P, rpw):
+    """Every wave boundary and P; beyond 16 of them: the first waves of threads 0 and 1 at per = 2,
+    a thread's second wave (3 rpw: that offset is written inside the thread's own loop, not taken from
+    the partial sums), the waves around 256, the last wave and P."""
+    bounds = list(range(0, P, rpw)) + [P]
+    if len(bounds) > 16:
+        nw = (P + rpw - 1) // rpw
+        bounds = sorted({0, rpw, 2 * rpw, 3 * rpw, 255 * rpw, min(256 * rpw, P), (nw - 1) * rpw, P})
+    assert len(bounds) <= 16
+    return bounds
 
 
 def _pack_np(on):
@@ -90,8 +110,7 @@ def _pattern(name, ranks, P, rng):
 def test_plan(ranks):
     C, rpw = _C(), _rpw()
     for P in _plan_sizes():
-        bounds = list(range(0, P, rpw)) + [P]
-        assert len(bounds) <= 16
+        bounds = _plan_bounds(P, rpw)
         for name in PATTERNS:
             rng = np.random.default_rng(1000 * ranks + P)
             on = _pattern(name, ranks, P, rng)
@@ -185,6 +204,37 @@ def test_gather_scatter(Ms):
                 w = _filled(P * M).view(P, M)
                 w[idx[u0:u1]] = comp[o + u0 * M:o + u1 * M].view(u1 - u0, M)
                 assert torch.equal(d, w), tag
+
+
+def test_gather_then_scatter_through_a_large_plan():
+    """256 waves and one row (union_offsets_kernel's threads own two waves each), a `half` union of
+    about 130k rows: rows_gather then rows_scatter through the plan's own `rows`, over a window that
+    starts and ends off a workgroup's 256 elements, bitwise against index_select / index_copy_ with
+    numpy's flatnonzero."""
+    C, mv = _C(), __import__("diff_gaussian_rasterization.multiview", fromlist=["x"])
+    P, Ms = 256 * _rpw() + 1, (3, 45, 1)
+    rng = np.random.default_rng(P)
+    on = _pattern("half", 1, P, rng)[0]
+    U, rows, _, _ = C.union_plan(torch.from_numpy(_pack_np(on)[None]).to(DEV), P)
+    idx = torch.from_numpy(np.flatnonzero(on)).to(DEV)
+    assert U == idx.numel() and 120_000 < U < 140_000
+    assert torch.equal(rows[:U].long(), idx)
+    u0, u1 = 100 * 256 + 37, U - 91
+    assert u0 % 256 and u1 % 256 and all(((u1 - u0) * M) % 256 and (u0 * M) % 256 for M in Ms)
+    src = [_bits((P, M), rng) for M in Ms]
+    off = mv.compact_layout(U, Ms)
+    compact = _filled(off[-1] + 16)
+    C.rows_gather([s.view(torch.float32) for s in src], rows, U, compact.view(torch.float32), window=(u0, u1))
+    want = _filled(off[-1] + 16)
+    for o, M, s in zip(off, Ms, src):
+        want[o + u0 * M:o + u1 * M] = s.index_select(0, idx[u0:u1]).reshape(-1)
+    assert torch.equal(compact, want)
+    dst = [_filled(P * M).view(P, M) for M in Ms]
+    C.rows_scatter([d.view(torch.float32) for d in dst], rows, U, compact.view(torch.float32), window=(u0, u1))
+    for M, s, d in zip(Ms, src, dst):
+        w = _filled(P * M).view(P, M)
+        w.index_copy_(0, idx[u0:u1], s.index_select(0, idx[u0:u1]))
+        assert torch.equal(d, w), M
 
 
 def test_gather_then_scatter_round_trip_leaves_other_rows():

@@ -83,6 +83,34 @@ def test_depth_sort_both_modes(wide):
     np.testing.assert_array_equal(ids, np.argsort(keys, kind="stable").astype(np.uint32))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("wide", [False, True])
+def test_depth_sort_past_one_block_of_group_rows(wide):
+    """2,100,003 keys, a fifth culled.  In the three-pass sort, 513 chunks of 4,096 keys are 33 groups
+    of 16 chunks, so the scatter prologue's loop over group rows (16 rows per iteration; one iteration
+    up to 1,048,576 keys) runs three times, the last with one row and fifteen clamped reads of it.
+    A clamped read counted would raise a digit's total, a row skipped would lower the offsets of every
+    chunk behind it: both move keys, as every group of 65,536 random keys holds every digit in use.
+    The forced four-pass sort (scanned totals, no group rows) sorts the same keys.  Exact against
+    numpy's stable argsort, and bit-identical when repeated."""
+    from diff_gaussian_rasterization import _C
+    n = 2_100_003
+    r = np.random.default_rng(23)
+    keys = _floats(r, n, 0.25, 40.0)
+    keys[r.permutation(n)[:n // 5]] = CULLED
+    want = np.argsort(keys, kind="stable").astype(np.uint32)
+    kt = torch.from_numpy(keys.view(np.int32).copy()).cuda()
+    was = _C.depth_wide()
+    _C.set_depth_wide(wide)
+    try:
+        a = _C.depth_sort(kt)
+        b = _C.depth_sort(kt)
+    finally:
+        _C.set_depth_wide(was)
+    np.testing.assert_array_equal(a.cpu().numpy().view(np.uint32), want)
+    assert torch.equal(a, b)
+
+
 def _wide_case():
     """Config 1's camera with 4,000 Gaussians whose depths span 0.3 ... 50,000 along view 0's ray (beyond
     the three-pass sort's factor of ~2^16), and the oracle on it."""

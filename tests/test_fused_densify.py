@@ -170,17 +170,73 @@ def _rows_per_workgroup():
 
 
 # ---- 1. kernel against the reference ----------------------------------------------------------------
+# densify_offsets_kernel: 256 threads, thread t owns the per = ceil(nw / 256) waves from t per on.  Up
+# to 256 waves (the first two sizes) a thread's loop runs at most once; the last three sizes, in
+# rows per wave (w), are 256 waves (every thread one wave: the serial pass sees 256 partial sums), 257
+# waves (per = 2: threads 0..127 two waves, thread 128 the last wave of one row, the others none)
+# and 770 waves less 19 rows (per = 4: threads 0..191 four waves, thread 192 two).
+LARGE_P = ("256w", "256w+1", "770w-19")
+
+
+def _sequence_cases():
+    """P x N x moments x world-size prune; the largest P with N = 2 and the world-size prune only."""
+    for P in (1037, "3wg+5") + LARGE_P:
+        for N in (2, 3):
+            for moments in (True, False):
+                for mss in (None, 20):
+                    if P != "770w-19" or (N == 2 and mss):
+                        yield pytest.param(P, N, moments, mss, id=f"{P}-{N}-{'moments' if moments else 'no-moments'}-"
+                                                                  f"{'world-size' if mss else 'no-world-size'}")
+
+
+def _decision_masks(raw, accum, denom, thr, N):
+    """The five decisions densify_decide_kernel counts per wave, from the float64 quantities (off
+    the thresholds, so the fp32 decisions of the reference are the same)."""
+    max_grad, min_opacity, extent, max_screen_size = thr
+    g, smax, sig = _quantities(raw, accum, denom)
+    hot = g >= max_grad
+    clone, split = hot & (smax <= PD * extent), hot & (smax > PD * extent)
+    low = sig < min_opacity
+    big = smax > 0.1 * extent if max_screen_size else torch.zeros_like(low)
+    bigchild = smax / (0.8 * N) > 0.1 * extent if max_screen_size else torch.zeros_like(low)
+    keep = ~(low | big)
+    return {"keep_orig": ~split & keep, "keep_clone": clone & keep, "split": split,
+            "keep_split": split & ~(low | bigchild), "clone": clone}
+
+
+def _assert_waves_beyond_the_first(masks, P, rpw):
+    """Every count is non-zero in a wave of a thread t >= 1 (its offset comes from the serial pass over
+    the partial sums) and, where threads own several waves, in the second wave of some thread (its
+    offset is the partial sum plus the thread's first wave) and in the wave before it."""
+    nw = (P + rpw - 1) // rpw
+    per = (nw + 255) // 256
+    wave = torch.arange(nw)
+    for name, m in masks.items():
+        cnt = torch.zeros(nw * rpw, dtype=torch.long)
+        cnt[:P] = m.long()
+        cnt = cnt.view(nw, rpw).sum(1)
+        assert bool((cnt[wave // per >= 1] > 0).any()), name
+        if per > 1:
+            second = (wave % per == 1) & (cnt > 0)
+            assert bool((second & (cnt[(wave - 1).clamp_min(0)] > 0)).any()), name
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("max_screen_size", [None, 20], ids=["no-world-size", "world-size"])
-@pytest.mark.parametrize("moments", [True, False], ids=["moments", "no-moments"])
-@pytest.mark.parametrize("N", [2, 3])
-@pytest.mark.parametrize("P", [1037, "3wg+5"])
+@pytest.mark.parametrize("P,N,moments,max_screen_size", list(_sequence_cases()))
 def test_matches_reference_sequence(P, N, moments, max_screen_size, monkeypatch):
     from diff_gaussian_rasterization import multiview as mv
+    large = P in LARGE_P
+    rpw = _rows_per_workgroup() // 4  # rows per wave
     if P == "3wg+5":
         P = 3 * _rows_per_workgroup() + 5
         assert P >= 10000
-    raw, accum, denom, state, thr = _case(P, N, max_screen_size, seed=P + 10 * N)
+    elif large:
+        P = {"256w": 256 * rpw, "256w+1": 256 * rpw + 1, "770w-19": 770 * rpw - 19}[P]
+    # (one f_rest coefficient at the large sizes: the plan does not read it, the copies stay quick)
+    raw, accum, denom, state, thr = _case(P, N, max_screen_size, seed=P + 10 * N, M=1 if large else 15)
+    masks = _decision_masks(raw, accum, denom, thr, N)
+    if large:
+        _assert_waves_beyond_the_first(masks, P, rpw)
     dev = torch.device("cuda", 0)
     step = torch.tensor(3.0)
     S = {k: {"step": step, "exp_avg": state[k][0].to(dev), "exp_avg_sq": state[k][1].to(dev)} for k in NAMES} \
@@ -200,6 +256,10 @@ def test_matches_reference_sequence(P, N, moments, max_screen_size, monkeypatch)
     print("counts:", counts)
     assert {k: counts[k] for k in ref_counts} == ref_counts and counts["P_before"] == P
     assert counts["cloned"] > 0 and counts["split"] > 0 and counts["pruned"] > 0
+    # the masks sliced by wave above are the reference's decisions
+    n = {k: int(m.sum()) for k, m in masks.items()}
+    assert (n["clone"], n["split"]) == (ref_counts["cloned"], ref_counts["split"])
+    assert n["keep_orig"] + n["keep_clone"] + N * n["keep_split"] == ref_counts["P_after"]
     # the children: the output rows whose source row (carried by f_dc) was split
     src_all = ref_T["f_dc"][:, 0, 0].long()
     g, smax, _ = _quantities(raw, accum, denom)
