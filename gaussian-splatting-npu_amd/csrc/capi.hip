@@ -905,9 +905,25 @@ int gsr_forward_views(int V, int P, int D, int M, const float* background, int w
     return forward_prealloc(sc, V, cam, vs, background, opt, caller, caller, debug, num_rendered, rendered);
 }
 
+int gsr_alpha_views(int V, int width, int height, char* const* image_buffers, float* const* out_alphas,
+                    gsr_stream_t stream)
+{
+    if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
+    if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID, "width and height must be > 0");
+    if (!image_buffers || !out_alphas) return fail(GSR_ERR_INVALID, "null per-view array");
+    for (int v = 0; v < V; v++)
+        if (!image_buffers[v] || !out_alphas[v]) return fail(GSR_ERR_INVALID, "null image buffer or alpha output");
+    const ImageLayout im = image_layout(width, height);
+    AlphaJob jobs[MAX_VIEWS];
+    for (int v = 0; v < V; v++) jobs[v] = {at<float>(image_buffers[v], im.off[IMG_FINAL_T]), out_alphas[v]};
+    HIP_TRY(launch_alpha_batch(jobs, V, (size_t)width * height, (hipStream_t)stream));
+    return GSR_OK;
+}
+
 // render_bwd's arguments for one view (P, R > 0), and the job of its backward tile order
 static RenderBwdArgs render_bwd_args(const Scene& sc, const ViewState& vs, int R, const float* background,
-                                     const float* dL_dpix, const float* dL_invdepths, OrderJob* order)
+                                     const float* dL_dpix, const float* dL_invdepths, const float* dL_dalphas,
+                                     OrderJob* order)
 {
     const int width = sc.width, height = sc.height;
     char *gb = vs.geometry, *ib = vs.image, *bb = vs.binning;
@@ -928,6 +944,7 @@ static RenderBwdArgs render_bwd_args(const Scene& sc, const ViewState& vs, int R
     r.n_contrib = at<uint32_t>(ib, im.off[IMG_N_CONTRIB]);
     r.dL_dpixels = dL_dpix;
     r.dL_invdepths = dL_invdepths;
+    r.dL_dalphas = dL_dalphas;
     r.grad_inst = at<float>(bb, b.off[BIN_GRAD_INST]);
     r.slot = slots_from_rect(tg.gx, tg.gy) ? nullptr : at<uint32_t>(bb, b.off[BIN_SLOT]);  // (render_bwd derives them)
     r.valid = at<uint32_t>(bb, b.off[BIN_VALID]);
@@ -985,9 +1002,11 @@ static int unpack_views(int V, int P, const int* R, const CameraArrays* ca, char
 
 // BACKWARD::render (rasterizer_impl.cu:399-418) of n views (arguments checked, P > 0; a view with R[v] == 0
 // has no instances, so no records to write, and is skipped): every view's backward tile order (longest
-// n_contrib first) in one launch, then their per-(tile, Gaussian) gradient records in one launch
+// n_contrib first) in one launch, then their per-(tile, Gaussian) gradient records in one launch.
+// dL_dalphas: null, or per view the gradient on the alpha output (gsr_alpha_views), null for a view without one
 static int backward_render(const Scene& sc, int n, const ViewState* vs, const int* R, const float* const* dL_dpix,
-                           const float* const* dL_invdepths, const float* background, bool debug, hipStream_t s)
+                           const float* const* dL_invdepths, const float* const* dL_dalphas, const float* background,
+                           bool debug, hipStream_t s)
 {
     OrderJob oj[MAX_VIEWS];
     RenderBwdArgs ra[MAX_VIEWS];
@@ -995,7 +1014,8 @@ static int backward_render(const Scene& sc, int n, const ViewState* vs, const in
     for (int v = 0; v < n; v++) {
         if (R[v] == 0) continue;
         const float* dL_inv = dL_invdepths ? dL_invdepths[v] : nullptr;
-        ra[nr] = render_bwd_args(sc, vs[v], R[v], background, dL_dpix[v], dL_inv, &oj[nr]);
+        const float* dL_da = dL_dalphas ? dL_dalphas[v] : nullptr;
+        ra[nr] = render_bwd_args(sc, vs[v], R[v], background, dL_dpix[v], dL_inv, dL_da, &oj[nr]);
         nr++;
     }
     if (nr) {
@@ -1088,16 +1108,16 @@ static int backward_preprocess(const Scene& sc, int V, const Camera* cam, const 
     return GSR_OK;
 }
 
-int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int width, int height,
-                        const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
-                        const float* opacities, const float* scales, float scale_modifier, const float* rotations,
-                        const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                        const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
-                        char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_invdepths,
-                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                        float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
-                        float* dL_dscale, float* dL_drot, bool antialiasing, bool debug, unsigned accumulate,
-                        gsr_stream_t stream)
+int gsr_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
+                       const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                       const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                       const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
+                       char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_invdepths,
+                       const float* dL_dalphas, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                       float* dL_dcolor, float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc,
+                       float* dL_dsh, float* dL_dscale, float* dL_drot, bool antialiasing, bool debug,
+                       unsigned accumulate, gsr_stream_t stream)
 {
     const Scene sc = {P, D, M, means3D, dc, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
                       cov3D_precomp, /*prefiltered=*/false, antialiasing, width, height};
@@ -1115,11 +1135,31 @@ int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int
     if (dL_invdepths && !dL_dinvdepth) return fail(GSR_ERR_INVALID, "dL_dinvdepth must be given with dL_invdepths");
     hipStream_t s = (hipStream_t)stream;
     if (R > 0) {  // (no instances: no records to write)
-        rc = backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr, background, debug, s);
+        rc = backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr,
+                             dL_dalphas ? &dL_dalphas : nullptr, background, debug, s);
         if (rc) return rc;
     }
     const BackwardOptions opt = {PREPROCESS_BWD_SINGLE, 0, P, dL_dconic, dL_dinvdepth};
     return backward_preprocess(sc, 1, &cam, &vs, &R, dL_invdepths != nullptr, &dL_dmean2D, g, opt, debug, s);
+}
+
+int gsr_backward_dc_acc(int P, int D, int M, int R, const float* background, int width, int height,
+                        const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                        const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                        const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                        const float* campos, float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
+                        char* binning_buffer, char* image_buffer, const float* dL_dpix, const float* dL_invdepths,
+                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                        float* dL_dinvdepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
+                        float* dL_dscale, float* dL_drot, bool antialiasing, bool debug, unsigned accumulate,
+                        gsr_stream_t stream)
+{
+    return gsr_backward_alpha(P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp, opacities,
+                              scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                              tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer, image_buffer, dL_dpix,
+                              dL_invdepths, /*dL_dalphas=*/nullptr, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                              dL_dinvdepth, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot, antialiasing,
+                              debug, accumulate, stream);
 }
 
 int gsr_backward_dc(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
@@ -1150,8 +1190,8 @@ int gsr_backward_render(int P, int R, const float* background, int width, int he
     Scene sc = {};
     sc.P = P; sc.width = width; sc.height = height;  // (all that BACKWARD::render reads)
     const ViewState vs = {geom_buffer, image_buffer, binning_buffer, 0, nullptr, nullptr, nullptr};
-    return backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr, background, debug,
-                           (hipStream_t)stream);
+    return backward_render(sc, 1, &vs, &R, &dL_dpix, dL_invdepths ? &dL_invdepths : nullptr, nullptr, background,
+                           debug, (hipStream_t)stream);
 }
 
 int gsr_backward_preprocess_views(int V, int P, int D, int M, const int* R, int width, int height,
@@ -1251,10 +1291,11 @@ int gsr_backward_camera_views(int V, int P, int D, int M, const int* R, int widt
     return GSR_OK;
 }
 
-int gsr_backward_render_views(int V, int P, const int* R, const float* background, int width, int height,
-                              char* const* geom_buffers, char* const* binning_buffers, char* const* image_buffers,
-                              const float* const* dL_dpix, const float* const* dL_invdepths, bool debug,
-                              gsr_stream_t stream)
+int gsr_backward_render_views_alpha(int V, int P, const int* R, const float* background, int width, int height,
+                                    char* const* geom_buffers, char* const* binning_buffers,
+                                    char* const* image_buffers, const float* const* dL_dpix,
+                                    const float* const* dL_invdepths, const float* const* dL_dalphas, bool debug,
+                                    gsr_stream_t stream)
 {
     if (V < 1 || V > MAX_VIEWS) return fail(GSR_ERR_INVALID, "V must be in [1, 16]");
     if (!R || !geom_buffers || !binning_buffers || !image_buffers || !dL_dpix)
@@ -1267,7 +1308,16 @@ int gsr_backward_render_views(int V, int P, const int* R, const float* backgroun
     if (rc) return rc;
     for (int v = 0; v < V; v++)
         if (!dL_dpix[v] || (dL_invdepths && !dL_invdepths[v])) return fail(GSR_ERR_INVALID, "null per-view gradient");
-    return backward_render(sc, V, vs, R, dL_dpix, dL_invdepths, background, debug, (hipStream_t)stream);
+    return backward_render(sc, V, vs, R, dL_dpix, dL_invdepths, dL_dalphas, background, debug, (hipStream_t)stream);
+}
+
+int gsr_backward_render_views(int V, int P, const int* R, const float* background, int width, int height,
+                              char* const* geom_buffers, char* const* binning_buffers, char* const* image_buffers,
+                              const float* const* dL_dpix, const float* const* dL_invdepths, bool debug,
+                              gsr_stream_t stream)
+{
+    return gsr_backward_render_views_alpha(V, P, R, background, width, height, geom_buffers, binning_buffers,
+                                           image_buffers, dL_dpix, dL_invdepths, /*dL_dalphas=*/nullptr, debug, stream);
 }
 
 int gsr_backward_views(int V, int P, int D, int M, const int* R, const float* background, int width, int height,
@@ -1282,8 +1332,28 @@ int gsr_backward_views(int V, int P, int D, int M, const int* R, const float* ba
                        float* dL_dscale, float* dL_drot, bool antialiasing, bool debug, unsigned accumulate,
                        gsr_stream_t stream)
 {
-    const int rc = gsr_backward_render_views(V, P, R, background, width, height, geom_buffers, binning_buffers,
-                                             image_buffers, dL_dpix, dL_invdepths, debug, stream);
+    return gsr_backward_views_alpha(V, P, D, M, R, background, width, height, means3D, dc, shs, colors_precomp,
+                                    opacities, scales, scale_modifier, rotations, cov3D_precomp, viewmatrices,
+                                    projmatrices, campos, tan_fovx, tan_fovy, radii, geom_buffers, binning_buffers,
+                                    image_buffers, dL_dpix, dL_invdepths, /*dL_dalphas=*/nullptr, dL_dmean2D, dL_dcolor,
+                                    dL_dopacity, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                                    antialiasing, debug, accumulate, stream);
+}
+
+int gsr_backward_views_alpha(int V, int P, int D, int M, const int* R, const float* background, int width, int height,
+                             const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                             const float* opacities, const float* scales, float scale_modifier,
+                             const float* rotations, const float* cov3D_precomp, const float* const* viewmatrices,
+                             const float* const* projmatrices, const float* const* campos, const float* tan_fovx,
+                             const float* tan_fovy, const int* const* radii, char* const* geom_buffers,
+                             char* const* binning_buffers, char* const* image_buffers, const float* const* dL_dpix,
+                             const float* const* dL_invdepths, const float* const* dL_dalphas,
+                             float* const* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D,
+                             float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                             bool antialiasing, bool debug, unsigned accumulate, gsr_stream_t stream)
+{
+    const int rc = gsr_backward_render_views_alpha(V, P, R, background, width, height, geom_buffers, binning_buffers,
+                                                   image_buffers, dL_dpix, dL_invdepths, dL_dalphas, debug, stream);
     if (rc || P <= 0) return rc;
     return gsr_backward_preprocess_views(V, P, D, M, R, width, height, means3D, dc, shs, colors_precomp, opacities,
                                          scales, scale_modifier, rotations, cov3D_precomp, viewmatrices,

@@ -75,6 +75,7 @@ struct RenderBwdArgs {
     const uint32_t* n_contrib;
     const float* dL_dpixels;
     const float* dL_invdepths;  // (1,H,W) or null
+    const float* dL_dalphas;    // (H,W) or null: the gradient on alpha = 1 - final_T (per view, wave-uniform)
     const uint32_t* slot;       // gradient-record slot of each sorted position
     uint32_t* valid;            // bit (slot & 31) of valid[slot >> 5] set for every record written (cleared by emit)
     float* grad_inst;           // f32x10[L]: one gradient record per (tile, Gaussian) entry, at its record slot
@@ -339,9 +340,16 @@ hipError_t launch_debug_keys_from_ranges(int T, const uint2* ranges, const uint3
                                          uint64_t* keys, hipStream_t s);
 
 // V views of one image size in one launch per VIEW_BATCH views (grid.y = view); render_bwd: every
-// view with dL_invdepths, or none
+// view with dL_invdepths, or none (dL_dalphas: any view, tested per view)
 hipError_t launch_render_fwd_batch(const RenderFwdArgs* a, int V, int T, hipStream_t s);
 hipError_t launch_render_bwd_batch(const RenderBwdArgs* a, int V, int T, hipStream_t s);
+// The alpha output of V views of n = H*W pixels each: out[i] = 1 - final_T[i] (final_T as render_fwd
+// stored it), one launch per VIEW_BATCH views (grid.y = view).
+struct AlphaJob {
+    const float* final_T;
+    float* out;
+};
+hipError_t launch_alpha_batch(const AlphaJob* jobs, int V, size_t n, hipStream_t s);
 hipError_t launch_preprocess_bwd_views(const PreprocessBwdViewsArgs& a, hipStream_t s);
 // one view through the batched kernel at one lane per Gaussian (a.radii set: the view's visibility)
 hipError_t launch_preprocess_bwd_single(const PreprocessBwdViewsArgs& a, hipStream_t s);

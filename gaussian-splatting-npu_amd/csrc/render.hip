@@ -755,13 +755,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD
     // Pixel state: every load issued before the first use (clamped addresses, masked after), so
     // the prologue costs one memory round trip instead of one per pixel.
     float Tf[4], dp0[4], dp1[4], dp2[4], dinv[4];
-    uint32_t lc[4];
+    uint32_t lc[4], pix[4];
     bool inside[4];
 #pragma unroll
     for (int p = 0; p < 4; p++) {
         const uint32_t px = qx0 + 2 * (p >> 1) + 4 * (p & 1);
         inside[p] = px < (uint32_t)a.W && qy < (uint32_t)a.H;
-        const uint32_t pix_id = inside[p] ? (uint32_t)a.W * qy + px : 0u;
+        const uint32_t pix_id = pix[p] = inside[p] ? (uint32_t)a.W * qy + px : 0u;
         Tf[p] = a.final_Ts[pix_id];
         lc[p] = a.n_contrib[pix_id];
         dp0[p] = a.dL_dpixels[0 * HW + pix_id];
@@ -769,9 +769,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD
         dp2[p] = a.dL_dpixels[2 * HW + pix_id];
         dinv[p] = HAS_INV ? a.dL_invdepths[pix_id] : 0.f;
     }
+    // the gradient on the alpha output (1 - final_T), for a view that has one: a wave-uniform branch
+    // (the pointer is a kernel argument of the view), its loads in flight with the ones above
+    const bool has_dalpha = a.dL_dalphas != nullptr;
+    float dalpha[4] = {0.f, 0.f, 0.f, 0.f};
+    if (has_dalpha) {
+#pragma unroll
+        for (int p = 0; p < 4; p++) dalpha[p] = a.dL_dalphas[pix[p]];
+    }
     const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
     BwdPair st[2];
-    float bgd[4];  // bg . dL/dpixel: the colour behind the last entry (the background, backward.cu:610-612)
+    // bg . dL/dpixel: the colour behind the last entry (the background, backward.cu:610-612), less
+    // dL/dalpha_out: d(1 - T_final)/dalpha_j = +T_final / (1 - alpha_j), the background's term with
+    // the opposite sign, so it rides in the same start value and costs nothing per list entry
+    float bgd[4];
 #pragma unroll
     for (int p = 0; p < 4; p++) {
         if (!inside[p]) {
@@ -780,6 +791,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD
             dp0[p] = dp1[p] = dp2[p] = dinv[p] = 0.f;
         }
         bgd[p] = bg0 * dp0[p] + bg1 * dp1[p] + bg2 * dp2[p];
+        if (has_dalpha) bgd[p] -= inside[p] ? dalpha[p] : 0.f;
     }
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -962,6 +974,57 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GSR_BWD
             __builtin_amdgcn_wave_barrier();  // s_rec / s_lq / s_part reuse in the next pass
         }
     }
+}
+
+// The alpha output: out[i] = 1 - final_T[i] over the n pixels of each view (grid.y = view), a
+// streaming pass of 8 B per pixel.  Work item i < n4 is one 16-B access (pixels 4i .. 4i + 3), the
+// items behind them the scalar tail; n4 = n / 4 where both of the view's arrays are 16-B aligned,
+// else 0 (every pixel a scalar item).  Grid-stride: the launcher caps the workgroups per launch.
+struct AlphaBatch {
+    AlphaJob v[VIEW_BATCH];
+    uint32_t n4[VIEW_BATCH];
+};
+
+__global__ void __launch_bounds__(256) alpha_kernel(const AlphaBatch B, uint32_t n)
+{
+    const AlphaJob a = B.v[blockIdx.y];
+    const uint32_t n4 = B.n4[blockIdx.y];
+    const uint32_t items = n4 + (n - 4u * n4);
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < items; i += stride) {
+        if (i < n4) {
+            const float4 t = reinterpret_cast<const float4*>(a.final_T)[i];
+            reinterpret_cast<float4*>(a.out)[i] = make_float4(1.f - t.x, 1.f - t.y, 1.f - t.z, 1.f - t.w);
+        } else {
+            const uint32_t k = 4u * n4 + (i - n4);
+            a.out[k] = 1.f - a.final_T[k];
+        }
+    }
+}
+
+hipError_t launch_alpha_batch(const AlphaJob* jobs, int V, size_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    if (n > 0x7FFFFFFFu) return hipErrorInvalidValue;  // (32-bit pixel indices, as the render kernels')
+    for (int v0 = 0; v0 < V; v0 += VIEW_BATCH) {
+        const int nv = min(VIEW_BATCH, V - v0);
+        AlphaBatch B = {};
+        uint32_t items = 0;
+        for (int v = 0; v < nv; v++) {
+            B.v[v] = jobs[v0 + v];
+            const bool aligned = (((uintptr_t)B.v[v].final_T | (uintptr_t)B.v[v].out) & 15u) == 0;
+            B.n4[v] = aligned ? (uint32_t)(n / 4) : 0u;
+            items = max(items, B.n4[v] + ((uint32_t)n - 4u * B.n4[v]));
+        }
+        // one wave for a 16x16 image; at 1080p ~2048 workgroups of 4 waves per launch (8 per CU)
+        const uint32_t block = items <= 64u ? 64u : 256u;
+        const uint32_t cap = max(1u, 2048u / (uint32_t)nv);
+        const uint32_t gx = min((items + block - 1) / block, cap);
+        hipLaunchKernelGGL(alpha_kernel, dim3(gx, (unsigned)nv), dim3(block), 0, s, B, (uint32_t)n);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_tile_order_batch(const OrderJob* jobs, int V, int T, hipStream_t s)

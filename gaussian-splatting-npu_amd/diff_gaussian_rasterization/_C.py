@@ -64,6 +64,14 @@ def _load(path=LIB_PATH):
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _b, _b, ctypes.c_uint, _vp]
     lib.gsr_backward_preprocess_views_range.argtypes = lib.gsr_backward_preprocess_views.argtypes[:-1] + [_i, _i, _vp]
     lib.gsr_backward_render_views.argtypes = [_i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _b, _vp]
+    # the alpha output: its forward pass, and the backward entry points with dL_dalphas after dL_invdepths
+    lib.gsr_alpha_views.argtypes = [_i, _i, _i, _vp, _vp, _vp]
+    lib.gsr_backward_alpha.argtypes = lib.gsr_backward_dc_acc.argtypes[:27] + [_vp] + \
+        lib.gsr_backward_dc_acc.argtypes[27:]
+    lib.gsr_backward_views_alpha.argtypes = lib.gsr_backward_views.argtypes[:28] + [_vp] + \
+        lib.gsr_backward_views.argtypes[28:]
+    lib.gsr_backward_render_views_alpha.argtypes = lib.gsr_backward_render_views.argtypes[:11] + [_vp] + \
+        lib.gsr_backward_render_views.argtypes[11:]
     lib.gsr_camera_grad_workspace_size.restype = _sz
     lib.gsr_camera_grad_workspace_size.argtypes = [_i, _i]
     lib.gsr_backward_camera_views.argtypes = [_i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
@@ -356,6 +364,67 @@ def rasterize_gaussians_views(background, means3D, colors, opacity, scales, rota
     return Ls, geoms, bins, imgs
 
 
+def render_alpha(imgBuffers, H, W, out=None):
+    """gsr_alpha_views: alpha = 1 - final_T of V views, (V,1,H,W) float32, from the image state of
+    their forwards (a list of imageBuffers of one image size, all on one GPU).  A view whose forward
+    had no Gaussians (P == 0: an empty imageBuffer) gets zeros.  `out`: a contiguous float32
+    (V,1,H,W) tensor on that GPU, written in full."""
+    V, H, W = len(imgBuffers), int(H), int(W)
+    if not 1 <= V <= 16:
+        raise RuntimeError(f"render_alpha: 1 to 16 views, got {V}")
+    dev = imgBuffers[0].device
+    _require_gpu(imgBuffers[0])
+    need = lib.gsr_image_buffer_size(W, H)
+    for t in imgBuffers:
+        if t.device != dev or t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() not in (0, need):
+            raise RuntimeError("render_alpha: imageBuffers must be the forward's uint8 state of a "
+                               f"{H}x{W} image on {dev}")
+    if out is None:
+        out = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (V, 1, H, W) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"out: expected a contiguous {torch.float32} tensor of shape {(V, 1, H, W)} on {dev}")
+    live = [v for v in range(V) if imgBuffers[v].numel()]
+    for v in range(V):
+        if not imgBuffers[v].numel():
+            out[v].zero_()
+    if live and H * W:
+        a = _Call(dev)
+        with torch.cuda.device(dev):
+            _check(lib.gsr_alpha_views(len(live), W, H, a.array([imgBuffers[v] for v in live]),
+                                       a.array([out[v] for v in live]), _stream(dev)))
+    return out
+
+
+def _alpha_grad(t, H, W, dev):
+    """One view's dL_dout_alpha, checked as dL_dout_color is (device, dtype; a contiguous copy if it
+    is strided) and for its shape, (1,H,W) or (H,W): the float32 tensor whose pointer the backward
+    takes, or None for an absent one."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) not in ((1, H, W), (H, W)):
+        got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"dL_dout_alpha must have shape {(1, H, W)}, got {got}")
+    if t.device != dev:
+        raise RuntimeError(f"dL_dout_alpha must be on {dev}, got {t.device}")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"dL_dout_alpha must be float32, got {t.dtype}")
+    return t.contiguous()
+
+
+def _alpha_grads(ts, V, H, W, dev):
+    """dL_dout_alpha of a batch -- a list of V per-view gradients with None for a view without one, or
+    one stacked (V,1,H,W) tensor -- as a list of checked tensors / None; None if no view has one."""
+    if ts is None:
+        return None
+    if isinstance(ts, torch.Tensor):
+        if tuple(ts.shape) != (V, 1, H, W):
+            raise RuntimeError(f"dL_dout_alpha must have shape {(V, 1, H, W)}, got {tuple(ts.shape)}")
+    elif len(ts) != V:
+        raise RuntimeError(f"dL_dout_alpha must have one entry per view ({V}), got {len(ts)}")
+    out = [_alpha_grad(ts[v], H, W, dev) for v in range(V)]
+    return out if any(t is not None for t in out) else None
+
+
 # The eight parameter gradients of the backward ops: accumulate= key, gsr.h GSR_ACC_* bit, and one
 # Gaussian's gradient as a function of M (its floats per Gaussian are the product; the gradient is
 # viewed as (P,) + that).  Fresh gradients are consecutive slices of ONE buffer in this order, which
@@ -430,7 +499,7 @@ def _grad_result(dL_dmeans2D, r, acc, has_dc):
 def rasterize_gaussians_backward(background, means3D, radii, colors, opacities, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                  dL_dout_invdepth, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                 antialiasing, debug, dc=None, accumulate=None):
+                                 antialiasing, debug, dc=None, accumulate=None, dL_dout_alpha=None):
     """RasterizeGaussiansBackwardNPU (rasterize_points.cu:126-223).  With `dc` (the separate-DC
     form) the result carries dL_ddc (P,1,3) before dL_dsh, as the accelerated upstream op returns
     it: (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales,
@@ -438,11 +507,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, opacities, 
 
     accumulate: optional {ACC_BITS key: tensor} -- the kernel ADDS that input's gradient into the
     given contiguous float32 tensor of the input's size (gsr_backward_dc_acc) and the result holds
-    None in its place."""
+    None in its place.
+
+    dL_dout_alpha (1,H,W): the gradient on render_alpha's output of this view (gsr_backward_alpha);
+    None is the call without it."""
     _require_gpu(means3D)
     dev = means3D.device
     P = means3D.size(0)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
+    dL_dout_alpha = _alpha_grad(dL_dout_alpha, H, W, dev)
     M, has_dc = _sh_split(sh, dc)
     # Render-pass gradients (one allocation): mean2D 3 | conic 4 | invdepth 1.
     # The HIP backward writes every element (no atomics, no pre-zeroing needed).
@@ -456,14 +529,18 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, opacities, 
         return _grad_result(dL_dmeans2D, r, acc, has_dc)
     a = _Call(dev)
     g_color, g_opacity, *g_rest = _grad_ptrs(r, M)
-    _check(lib.gsr_backward_dc_acc(
+    if dL_dout_alpha is None:
+        entry, g_alpha = lib.gsr_backward_dc_acc, ()
+    else:
+        entry, g_alpha = lib.gsr_backward_alpha, (a.p(dL_dout_alpha, "dL_dout_alpha"),)
+    _check(entry(
         P, int(degree), M, int(R), a.p(background, "bg"), W, H,
         *a.gaussians(means3D, dc, sh, colors, opacities, scales, scale_modifier, rotations, cov3D_precomp),
         a.p(viewmatrix, "viewmatrix"), a.p(projmatrix, "projmatrix"), a.p(campos, "campos"), float(tan_fovx),
         float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(),
         binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
         a.p(dL_dout_color, "dL_dout_color"), a.p(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None,
-        dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), g_opacity, g_color,
+        *g_alpha, dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), g_opacity, g_color,
         dL_dinvdepths.data_ptr() if has_inv else None, *g_rest, bool(antialiasing), bool(debug), mask, _stream(dev)))
     return _grad_result(dL_dmeans2D, r, acc, has_dc)
 
@@ -472,7 +549,8 @@ def _backward_views(render, means3D, radii, colors, opacities, scales, rotations
                     viewmatrices, projmatrices, tan_fovx, tan_fovy, W, H, sh, degree, campos, geomBuffers, Rs,
                     binningBuffers, has_inv, antialiasing, debug, dc, accumulate, on_chunk):
     """The batched backward behind rasterize_gaussians_backward_views (render = (background,
-    imageBuffers, dL_dout_colors, dL_dout_invdepths or None): the views' BACKWARD::render runs here)
+    imageBuffers, dL_dout_colors, dL_dout_invdepths or None, dL_dout_alphas: None or the checked
+    per-view list of _alpha_grads, which selects the *_alpha entry points): the views' BACKWARD::render runs here)
     and rasterize_gaussians_preprocess_backward_views (render = None: it already ran).  Without
     on_chunk one native call (gsr_backward_views / gsr_backward_preprocess_views); with on_chunk =
     (chunks, fn) gsr_backward_render_views if `render`, then gsr_backward_preprocess_views_range over
@@ -491,14 +569,18 @@ def _backward_views(render, means3D, radii, colors, opacities, scales, rotations
     state = (*vb.cams, vb.radii, vb.geoms, vb.bins)
     grads = (a.array(dL_dmeans2D), *_grad_ptrs(r, M), bool(antialiasing), bool(debug), mask)
     if render is not None:
-        background, imageBuffers, dL_dout_colors, dL_dout_invdepths = render
+        background, imageBuffers, dL_dout_colors, dL_dout_invdepths, dL_dout_alphas = render
         frame = (a.p(background, "bg"), W, H)
         pix = (a.array(imageBuffers), a.array(dL_dout_colors, "dL_dout_color"),
                a.array(dL_dout_invdepths, "dL_dout_invdepth") if has_inv else None)
+        both, half = lib.gsr_backward_views, lib.gsr_backward_render_views
+        if dL_dout_alphas is not None:
+            pix += (a.array(dL_dout_alphas, "dL_dout_alpha"),)
+            both, half = lib.gsr_backward_views_alpha, lib.gsr_backward_render_views_alpha
         if on_chunk is None:
-            _check(lib.gsr_backward_views(*sizes, *frame, *gauss, *state, *pix, *grads, _stream(dev)))
+            _check(both(*sizes, *frame, *gauss, *state, *pix, *grads, _stream(dev)))
             return _grad_result(dL_dmeans2D, r, acc, has_dc)
-        _check(lib.gsr_backward_render_views(V, P, vb.R, *frame, vb.geoms, vb.bins, *pix, bool(debug), _stream(dev)))
+        _check(half(V, P, vb.R, *frame, vb.geoms, vb.bins, *pix, bool(debug), _stream(dev)))
     preprocess = (*sizes, int(W), int(H), *gauss, *state, bool(has_inv), *grads)
     if on_chunk is None:
         _check(lib.gsr_backward_preprocess_views(*preprocess, _stream(dev)))
@@ -517,7 +599,7 @@ def rasterize_gaussians_backward_views(background, means3D, radii, colors, opaci
                                        scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tan_fovx, tan_fovy,
                                        dL_dout_colors, dL_dout_invdepths, sh, degree, campos, geomBuffers, Rs,
                                        binningBuffers, imageBuffers, antialiasing, debug, dc=None, accumulate=None,
-                                       on_chunk=None):
+                                       on_chunk=None, dL_dout_alpha=None):
     """Backward of a batch of V views (gsr_backward_views): per-view lists of the forward's state
     (radii (P,), camera, buffers, num_rendered) and dL_dout_colors (V,3,H,W), dL_dout_invdepths
     (V,1,H,W) or None.  Returns (dL_dmeans2D (V,P,3), dL_dcolors, dL_dopacity, dL_dmeans3D,
@@ -527,25 +609,40 @@ def rasterize_gaussians_backward_views(background, means3D, radii, colors, opaci
     (gsr_backward_render_views, then gsr_backward_preprocess_views_range per range) and fn(g0, g1,
     grads) is called after each launch is enqueued, grads = {input name: its gradient tensor (P,...)}
     (the caller's accumulate targets or the fresh buffers): rows [g0, g1) are final from then on in
-    stream order (multiview.overlapped_allreduce)."""
+    stream order (multiview.overlapped_allreduce).
+    dL_dout_alpha: the gradients on render_alpha's output (gsr_backward_views_alpha) as a list of V
+    (1,H,W) tensors with None for a view without one, or one stacked (V,1,H,W) tensor; None is the
+    call without it."""
     V = len(geomBuffers)
     H, W = dL_dout_colors.size(2), dL_dout_colors.size(3)
+    dL_dout_alpha = _alpha_grads(dL_dout_alpha, V, H, W, means3D.device)
     has_inv = dL_dout_invdepths is not None and dL_dout_invdepths.numel() != 0
     if dL_dout_colors.shape != (V, 3, H, W) or (has_inv and dL_dout_invdepths.shape != (V, 1, H, W)):
         raise RuntimeError("dL_dout_colors must be (V,3,H,W) and dL_dout_invdepths (V,1,H,W)")
-    return _backward_views((background, imageBuffers, dL_dout_colors, dL_dout_invdepths), means3D, radii, colors,
-                           opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
+    return _backward_views((background, imageBuffers, dL_dout_colors, dL_dout_invdepths, dL_dout_alpha), means3D,
+                           radii, colors, opacities, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                            tan_fovx, tan_fovy, W, H, sh, degree, campos, geomBuffers, Rs, binningBuffers, has_inv,
                            antialiasing, debug, dc, accumulate, on_chunk)
 
 
 def rasterize_gaussians_render_backward(background, P, R, geomBuffer, binningBuffer, imageBuffer, dL_dout_color,
-                                        dL_dout_invdepth, debug):
+                                        dL_dout_invdepth, debug, dL_dout_alpha=None):
     """BACKWARD::render of one view (gsr_backward_render): its per-(tile, Gaussian) gradient
-    records into binningBuffer, for rasterize_gaussians_preprocess_backward_views later."""
+    records into binningBuffer, for rasterize_gaussians_preprocess_backward_views later.
+    dL_dout_alpha (1,H,W): the gradient on render_alpha's output of this view
+    (gsr_backward_render_views_alpha with one view); None is the call without it."""
     a = _Call(dL_dout_color.device)
     H, W = dL_dout_color.size(1), dL_dout_color.size(2)
     has_inv = dL_dout_invdepth is not None and dL_dout_invdepth.numel() != 0
+    dL_dout_alpha = _alpha_grad(dL_dout_alpha, H, W, a.dev)
+    if dL_dout_alpha is not None:
+        one = lambda t, name=None: a.array([t], name)  # noqa: E731
+        _check(lib.gsr_backward_render_views_alpha(
+            1, int(P), (_i * 1)(int(R)), a.p(background, "bg"), W, H, one(geomBuffer),
+            one(binningBuffer), one(imageBuffer), one(dL_dout_color, "dL_dout_color"),
+            one(dL_dout_invdepth, "dL_dout_invdepth") if has_inv else None, one(dL_dout_alpha, "dL_dout_alpha"),
+            bool(debug), _stream(a.dev)))
+        return has_inv
     _check(lib.gsr_backward_render(int(P), int(R), a.p(background, "bg"), W, H, geomBuffer.data_ptr(),
                                    binningBuffer.data_ptr() if binningBuffer.numel() else None,
                                    imageBuffer.data_ptr(), a.p(dL_dout_color, "dL_dout_color"),

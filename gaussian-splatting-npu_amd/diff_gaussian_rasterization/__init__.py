@@ -303,7 +303,10 @@ class GaussianRasterizationSettings(NamedTuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, dc=None):
+                        raster_settings, dc=None, return_alpha=False):
+    """return_alpha: the node with the fourth output (_RasterizeGaussiansAlpha); the default is the
+    reference's node, untouched."""
+    node = _RasterizeGaussiansAlpha if return_alpha else _RasterizeGaussians
     batch = getattr(_state, "deferred", None)
     inputs = (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, dc)
     if batch is not None and torch.is_grad_enabled() and any(
@@ -313,10 +316,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
         # batch's exit runs it once); means2D (or a stand-in) carries the view's backward call
         anchor = means2D if means2D.requires_grad else torch.zeros((0,), requires_grad=True)
         det = [None if t is None else t.detach() for t in inputs]
-        return _RasterizeGaussians.apply(det[0], anchor, det[1], det[2], det[3], det[4], det[5], det[6],
-                                         raster_settings, det[7], (batch, inputs, means2D))
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, dc)
+        return node.apply(det[0], anchor, det[1], det[2], det[3], det[4], det[5], det[6], raster_settings, det[7],
+                          (batch, inputs, means2D))
+    return node.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                      raster_settings, dc)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -328,6 +331,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, dc=None, deferred=None):
+        return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                            cov3Ds_precomp, raster_settings, dc, deferred)[:3]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 raster_settings, dc=None, deferred=None):
+        """forward's outputs and, behind them, the call's image state (what the alpha nodes read)."""
         s = raster_settings
         num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, invdepths = _C.rasterize_gaussians(
             s.bg, means3D, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
@@ -346,10 +356,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities,
                               geomBuffer, binningBuffer, imgBuffer, dc)
-        return color, radii, invdepths
+        return color, radii, invdepths, imgBuffer
 
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth):
+        return _RasterizeGaussians._backward(ctx, grad_out_color, grad_out_depth, None)
+
+    @staticmethod
+    def _backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha):
+        """backward; grad_out_alpha: the alpha nodes' fourth gradient (None: the call without it)."""
         s = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, geomBuffer,
          binningBuffer, imgBuffer, dc) = ctx.saved_tensors
@@ -362,7 +377,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             dev = means3D.device
             has_inv = _C.rasterize_gaussians_render_backward(
                 s.bg, means3D.size(0), ctx.num_rendered, geomBuffer, binningBuffer, imgBuffer, grad_out_color,
-                grad_out_depth, s.debug)
+                grad_out_depth, s.debug, dL_dout_alpha=grad_out_alpha)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
             batch, caller_inputs, i_m2 = ctx.deferred
@@ -384,8 +399,30 @@ class _RasterizeGaussians(torch.autograd.Function):
                 s.bg, means3D, radii, colors_precomp, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
                 s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_out_color, grad_out_depth, sh, s.sh_degree,
                 s.campos, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, s.antialiasing, s.debug, dc=dc,
-                accumulate=accumulate)
+                accumulate=accumulate, dL_dout_alpha=grad_out_alpha)
         return _autograd_order(grads) + (None,)
+
+
+def _alpha_output(imgBuffers, s):
+    """alpha = 1 - final_T (V,1,H,W) of the views whose forward left `imgBuffers` (settings s)."""
+    return _C.render_alpha(imgBuffers, s.image_height, s.image_width)
+
+
+class _RasterizeGaussiansAlpha(torch.autograd.Function):
+    """_RasterizeGaussians with a fourth output, alpha = 1 - final_T (1,H,W): the accumulated opacity of
+    each pixel, read from the forward's image state by one elementwise launch (gsr_alpha_views).  Its
+    gradient enters the same BACKWARD::render as the colour's (gsr_backward_alpha: it is subtracted
+    from bg . dL/dpixel, the walk's start value), so every input gradient carries it; a None gradient
+    stays None and takes the backward of the node without alpha."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        color, radii, invdepths, imgBuffer = _RasterizeGaussians._forward(ctx, *args)
+        return color, radii, invdepths, _alpha_output([imgBuffer], ctx.raster_settings)[0]
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_out_alpha):
+        return _RasterizeGaussians._backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha)
 
 
 def _camera_guard(keyword):
@@ -408,13 +445,14 @@ def _camera_triple(keyword, viewmatrix, projmatrix, campos, lead=()):
 
 
 def rasterize_gaussians_camera(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                               raster_settings, dc, viewmatrix, projmatrix, campos):
+                               raster_settings, dc, viewmatrix, projmatrix, campos, return_alpha=False):
     """rasterize_gaussians with the settings' camera replaced by three tensors that take part in
     autograd (GaussianRasterizer.forward's camera=)."""
     _camera_guard("camera=")
     _camera_triple("camera=", viewmatrix, projmatrix, campos)
-    return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                           cov3Ds_precomp, raster_settings, dc, viewmatrix, projmatrix, campos)
+    node = _RasterizeGaussiansCameraAlpha if return_alpha else _RasterizeGaussiansCamera
+    return node.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                      raster_settings, dc, viewmatrix, projmatrix, campos)
 
 
 class _RasterizeGaussiansCamera(torch.autograd.Function):
@@ -426,15 +464,26 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, dc, viewmatrix, projmatrix, campos):
+        return _RasterizeGaussiansCamera._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales,
+                                                  rotations, cov3Ds_precomp, raster_settings, dc, viewmatrix,
+                                                  projmatrix, campos)[:3]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 raster_settings, dc, viewmatrix, projmatrix, campos):
         cam = tuple(t.detach().contiguous() for t in (viewmatrix, projmatrix, campos))
         s = raster_settings._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2])
-        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                           cov3Ds_precomp, s, dc)
+        return _RasterizeGaussians._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                            cov3Ds_precomp, s, dc)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_out_depth):
+        return _RasterizeGaussiansCamera._backward(ctx, grad_out_color, grad_out_depth, None)
+
+    @staticmethod
+    def _backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha):
         _camera_guard("camera=")
-        grads = _RasterizeGaussians.backward(ctx, grad_out_color, grad_radii, grad_out_depth)[:10]
+        grads = _RasterizeGaussians._backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha)[:10]
         if not any(ctx.needs_input_grad[10:13]):
             return grads + (None, None, None)
         s = ctx.raster_settings
@@ -448,6 +497,20 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
             has_inv, s.antialiasing, s.debug, dc=dc)
         cam = (g_view[0], g_proj[0], g_campos[0])
         return grads + tuple(g if need else None for g, need in zip(cam, ctx.needs_input_grad[10:13]))
+
+
+class _RasterizeGaussiansCameraAlpha(torch.autograd.Function):
+    """_RasterizeGaussiansCamera with the alpha output of _RasterizeGaussiansAlpha: the camera gradient
+    reads the gradient records, which carry the alpha term."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        color, radii, invdepths, imgBuffer = _RasterizeGaussiansCamera._forward(ctx, *args)
+        return color, radii, invdepths, _alpha_output([imgBuffer], ctx.raster_settings)[0]
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth, grad_out_alpha):
+        return _RasterizeGaussiansCamera._backward(ctx, grad_out_color, grad_out_depth, grad_out_alpha)
 
 
 def fused_activations(scaling, rotation, opacity):
@@ -511,17 +574,26 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, s.viewmatrix, s.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None, camera=None):
+                cov3D_precomp=None, dc=None, camera=None, return_alpha=False):
         """``dc`` (P,1,3), keyword only in practice (gaussian_renderer/__init__.py:91-100): SH
         coefficient 0, with ``shs`` then holding coefficients 1.. (features_rest).
         ``camera`` = (viewmatrix (4,4), projmatrix (4,4), campos (3,)): float32 tensors on the device
         that replace the settings' three for this call and take part in autograd (pose refinement:
         multiview.pose_camera); those that require grad receive dL/dviewmatrix, dL/dprojmatrix and
-        dL/dcampos, everything else is what the call without ``camera`` gives."""
+        dL/dcampos, everything else is what the call without ``camera`` gives.
+        ``return_alpha``: return (color, radii, invdepth, alpha) with alpha (1,H,W) float32 = 1 - final_T,
+        the opacity each pixel accumulated -- a differentiable output of the same node (silhouette and
+        mask losses, compositing over a background chosen after the render: color + (1 - alpha) * bg'
+        for a render with a zero background); the other three are what the call without it returns."""
         args = _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
         if camera is not None:
             viewmatrix, projmatrix, campos = camera
+            if return_alpha:
+                return rasterize_gaussians_camera(*args, self.raster_settings, dc, viewmatrix, projmatrix, campos,
+                                                  return_alpha=True)
             return rasterize_gaussians_camera(*args, self.raster_settings, dc, viewmatrix, projmatrix, campos)
+        if return_alpha:
+            return rasterize_gaussians(*args, self.raster_settings, dc, return_alpha=True)
         return rasterize_gaussians(*args, self.raster_settings, dc)
 
 
@@ -546,9 +618,10 @@ def _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, ro
 
 
 def rasterize_views(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                    raster_settings, dc=None):
-    return _RasterizeViews.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                 cov3Ds_precomp, tuple(raster_settings), dc)
+                    raster_settings, dc=None, return_alpha=False):
+    node = _RasterizeViewsAlpha if return_alpha else _RasterizeViews
+    return node.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                      tuple(raster_settings), dc)
 
 
 class _RasterizeViews(torch.autograd.Function):
@@ -565,6 +638,13 @@ class _RasterizeViews(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, dc=None):
+        return _RasterizeViews._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                        cov3Ds_precomp, raster_settings, dc)[:3]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 raster_settings, dc=None):
+        """forward's outputs and, behind them, the views' image states (what the alpha nodes read)."""
         V = len(raster_settings)
         s0 = raster_settings[0]
         H, W, P = s0.image_height, s0.image_width, means3D.size(0)
@@ -589,10 +669,15 @@ class _RasterizeViews(torch.autograd.Function):
                               *[t for st in state for t in st[1:]])
         ctx.acc_inputs = _named_inputs(means3D, dc, sh, opacities, scales, rotations, cov3Ds_precomp,
                                        colors_precomp) if getattr(_state, "accumulate", False) else None
-        return colors, radii, invdepths
+        return colors, radii, invdepths, imgs
 
     @staticmethod
     def backward(ctx, grad_colors, _grad_radii, grad_invdepths):
+        return _RasterizeViews._backward(ctx, grad_colors, grad_invdepths, None)
+
+    @staticmethod
+    def _backward(ctx, grad_colors, grad_invdepths, grad_alphas):
+        """backward; grad_alphas (V,1,H,W): the alpha nodes' fourth gradient (None: the call without it)."""
         ss = ctx.raster_settings
         s0 = ss[0]
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, opacities, dc,
@@ -615,21 +700,36 @@ class _RasterizeViews(torch.autograd.Function):
                     s0.scale_modifier, cov3Ds_precomp, [s.viewmatrix for s in ss], [s.projmatrix for s in ss],
                     [s.tanfovx for s in ss], [s.tanfovy for s in ss], grad_colors, grad_invdepths, sh, s0.sh_degree,
                     [s.campos for s in ss], bufs[0::3], ctx.num_rendered, bufs[1::3], bufs[2::3], s0.antialiasing,
-                    s0.debug, dc=dc, accumulate=accumulate, on_chunk=on_chunk)
+                    s0.debug, dc=dc, accumulate=accumulate, on_chunk=on_chunk, dL_dout_alpha=grad_alphas)
             finally:
                 if done is not None:
                     done()
         return _autograd_order(grads)
 
 
+class _RasterizeViewsAlpha(torch.autograd.Function):
+    """_RasterizeViews with a fourth output, the views' alphas (V,1,H,W) (_RasterizeGaussiansAlpha per
+    view: one gsr_alpha_views launch for the batch; gsr_backward_views_alpha takes their gradient)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        colors, radii, invdepths, imgs = _RasterizeViews._forward(ctx, *args)
+        return colors, radii, invdepths, _alpha_output(imgs, ctx.raster_settings[0])
+
+    @staticmethod
+    def backward(ctx, grad_colors, _grad_radii, grad_invdepths, grad_alphas):
+        return _RasterizeViews._backward(ctx, grad_colors, grad_invdepths, grad_alphas)
+
+
 def rasterize_views_camera(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                           raster_settings, dc, viewmatrices, projmatrices, campos):
+                           raster_settings, dc, viewmatrices, projmatrices, campos, return_alpha=False):
     """rasterize_views with the views' cameras replaced by stacked tensors (V,4,4), (V,4,4), (V,3)
     that take part in autograd (MultiViewRasterizer.forward's cameras=)."""
     _camera_guard("cameras=")
     _camera_triple("cameras=", viewmatrices, projmatrices, campos, lead=(len(raster_settings),))
-    return _RasterizeViewsCamera.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                       cov3Ds_precomp, tuple(raster_settings), dc, viewmatrices, projmatrices, campos)
+    node = _RasterizeViewsCameraAlpha if return_alpha else _RasterizeViewsCamera
+    return node.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                      tuple(raster_settings), dc, viewmatrices, projmatrices, campos)
 
 
 class _RasterizeViewsCamera(torch.autograd.Function):
@@ -640,16 +740,27 @@ class _RasterizeViewsCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, dc, viewmatrices, projmatrices, campos):
+        return _RasterizeViewsCamera._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                              cov3Ds_precomp, raster_settings, dc, viewmatrices, projmatrices,
+                                              campos)[:3]
+
+    @staticmethod
+    def _forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                 raster_settings, dc, viewmatrices, projmatrices, campos):
         ctx.cameras = tuple(t.detach().contiguous() for t in (viewmatrices, projmatrices, campos))
         ss = tuple(s._replace(viewmatrix=ctx.cameras[0][v], projmatrix=ctx.cameras[1][v], campos=ctx.cameras[2][v])
                    for v, s in enumerate(raster_settings))
-        return _RasterizeViews.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                       cov3Ds_precomp, ss, dc)
+        return _RasterizeViews._forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                        cov3Ds_precomp, ss, dc)
 
     @staticmethod
     def backward(ctx, grad_colors, grad_radii, grad_invdepths):
+        return _RasterizeViewsCamera._backward(ctx, grad_colors, grad_invdepths, None)
+
+    @staticmethod
+    def _backward(ctx, grad_colors, grad_invdepths, grad_alphas):
         _camera_guard("cameras=")
-        grads = _RasterizeViews.backward(ctx, grad_colors, grad_radii, grad_invdepths)
+        grads = _RasterizeViews._backward(ctx, grad_colors, grad_invdepths, grad_alphas)
         if not any(ctx.needs_input_grad[10:13]):
             return grads + (None, None, None)
         ss = ctx.raster_settings
@@ -662,6 +773,19 @@ class _RasterizeViewsCamera(torch.autograd.Function):
             [s.tanfovx for s in ss], [s.tanfovy for s in ss], s0.image_height, s0.image_width, sh, s0.sh_degree,
             bufs[0::3], ctx.num_rendered, bufs[1::3], has_inv, s0.antialiasing, s0.debug, dc=dc)
         return grads + tuple(g if need else None for g, need in zip(cam, ctx.needs_input_grad[10:13]))
+
+
+class _RasterizeViewsCameraAlpha(torch.autograd.Function):
+    """_RasterizeViewsCamera with the alpha output of _RasterizeViewsAlpha."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        colors, radii, invdepths, imgs = _RasterizeViewsCamera._forward(ctx, *args)
+        return colors, radii, invdepths, _alpha_output(imgs, ctx.raster_settings[0])
+
+    @staticmethod
+    def backward(ctx, grad_colors, _grad_radii, grad_invdepths, grad_alphas):
+        return _RasterizeViewsCamera._backward(ctx, grad_colors, grad_invdepths, grad_alphas)
 
 
 class MultiViewRasterizer(nn.Module):
@@ -687,11 +811,13 @@ class MultiViewRasterizer(nn.Module):
         self.raster_settings = ss
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, dc=None, cameras=None):
+                cov3D_precomp=None, dc=None, cameras=None, return_alpha=False):
         """``cameras``: the views' cameras as stacked float32 tensors (viewmatrices (V,4,4),
         projmatrices (V,4,4), campos (V,3)) or a list of V (viewmatrix, projmatrix, campos) triples;
         they replace the settings' for this call and take part in autograd
-        (GaussianRasterizer.forward's ``camera``, per view)."""
+        (GaussianRasterizer.forward's ``camera``, per view).
+        ``return_alpha``: return (colors, radii, invdepths, alphas) with alphas (V,1,H,W) float32, each
+        view's GaussianRasterizer.forward(return_alpha=True) alpha; differentiable."""
         args = _checked_inputs(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, dc)
         if cameras is not None:
             if len(cameras) == 3 and all(isinstance(t, torch.Tensor) and t.dim() >= 2 for t in cameras):
@@ -700,7 +826,12 @@ class MultiViewRasterizer(nn.Module):
                 if len(cameras) != len(self.raster_settings):
                     raise RuntimeError(f"cameras=: {len(self.raster_settings)} views, got {len(cameras)} cameras")
                 viewmatrices, projmatrices, campos = (torch.stack([c[k] for c in cameras]) for k in range(3))
+            if return_alpha:
+                return rasterize_views_camera(*args, self.raster_settings, dc, viewmatrices, projmatrices, campos,
+                                              return_alpha=True)
             return rasterize_views_camera(*args, self.raster_settings, dc, viewmatrices, projmatrices, campos)
+        if return_alpha:
+            return rasterize_views(*args, self.raster_settings, dc, return_alpha=True)
         return rasterize_views(*args, self.raster_settings, dc)
 
 

@@ -345,6 +345,63 @@ int gsr_backward_preprocess_views_range(int V, int P, int D, int M, const int* R
                                         bool antialiasing, bool debug, unsigned accumulate, int g_begin, int g_end,
                                         gsr_stream_t stream);
 
+/* The alpha output, alpha = 1 - final_T per pixel: the opacity a pixel accumulated, i.e. the
+ * reference's render with colour 1 and background 0 (FORWARD::render, forward.cu:277-400: T behind
+ * the last contributor, the `final_T` that the forward keeps for the backward).  The reference does
+ * not return it; a silhouette or mask loss and compositing over a per-iteration background need it.
+ * gsr_alpha_views: valid after any forward (gsr_forward*, gsr_forward_render, gsr_forward_views) into
+ * those image buffers, before the next forward into them; it only reads the state.  Per-view host
+ * arrays of V device pointers: image_buffers, and out_alphas (H*W floats each), every one fully
+ * written -- zeros for a view with num_rendered == 0, whose final_T is 1.  One elementwise launch
+ * per 8 views (8 B per pixel).  V outside [1, 16], width or height <= 0, a NULL array or a NULL
+ * element: GSR_ERR_INVALID, before any HIP call.  (P == 0 forwards return before they write the
+ * image state: there is no alpha to read.)  Asynchronous; never throws (status + gsr_last_error). */
+int gsr_alpha_views(int V, int width, int height, char* const* image_buffers, float* const* out_alphas,
+                    gsr_stream_t stream);
+
+/* The backward entry points with a gradient on the alpha output: gsr_backward_alpha is
+ * gsr_backward_dc_acc, gsr_backward_views_alpha is gsr_backward_views and
+ * gsr_backward_render_views_alpha is gsr_backward_render_views (with V = 1: gsr_backward_render),
+ * each with dL_dalphas directly after dL_invdepths -- (H,W) floats, the loss's gradient with respect
+ * to gsr_alpha_views' output of that view; for the batched two a host array of V device pointers.
+ * BACKWARD::render (backward.cu:601-612) gives dL/dalpha_j the background's term
+ * -T_final / (1 - alpha_j) (bg . dL/dpixel); d(1 - T_final)/dalpha_j = +T_final / (1 - alpha_j), so the
+ * alpha gradient enters as bg . dL/dpixel - dL_dalphas in that term and nowhere else: the gradient
+ * records, and with them the parameter gradients, dL_dmean2D and gsr_backward_camera_views' outputs,
+ * carry it with no further argument.  dL_dalphas NULL (for the batched two also any element NULL,
+ * views with and without one mixed freely): that view has no alpha term and gets the bits the entry
+ * point without the argument gives; those entry points pass NULL here and are otherwise this code.
+ * Argument checks, return codes and messages are those of gsr_backward_dc_acc, gsr_backward_views and
+ * gsr_backward_render_views; no check is added for dL_dalphas.  Asynchronous; never throw (status +
+ * gsr_last_error). */
+int gsr_backward_alpha(int P, int D, int M, int R, const float* background, int width, int height,
+                       const float* means3D, const float* dc, const float* shs,
+                       const float* colors_precomp, const float* opacities, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos,
+                       float tan_fovx, float tan_fovy, const int* radii, char* geom_buffer,
+                       char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                       const float* dL_invdepths, const float* dL_dalphas, float* dL_dmean2D,
+                       float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dinvdepth,
+                       float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
+                       float* dL_drot, bool antialiasing, bool debug, unsigned accumulate, gsr_stream_t stream);
+int gsr_backward_views_alpha(int V, int P, int D, int M, const int* R, const float* background, int width, int height,
+                             const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+                             const float* opacities, const float* scales, float scale_modifier,
+                             const float* rotations, const float* cov3D_precomp, const float* const* viewmatrices,
+                             const float* const* projmatrices, const float* const* campos, const float* tan_fovx,
+                             const float* tan_fovy, const int* const* radii, char* const* geom_buffers,
+                             char* const* binning_buffers, char* const* image_buffers, const float* const* dL_dpix,
+                             const float* const* dL_invdepths, const float* const* dL_dalphas,
+                             float* const* dL_dmean2D, float* dL_dcolor, float* dL_dopacity, float* dL_dmean3D,
+                             float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                             bool antialiasing, bool debug, unsigned accumulate, gsr_stream_t stream);
+int gsr_backward_render_views_alpha(int V, int P, const int* R, const float* background, int width, int height,
+                                    char* const* geom_buffers, char* const* binning_buffers,
+                                    char* const* image_buffers, const float* const* dL_dpix,
+                                    const float* const* dL_invdepths, const float* const* dL_dalphas, bool debug,
+                                    gsr_stream_t stream);
+
 /* The camera gradient of V <= 16 views: dL/dviewmatrix, dL/dprojmatrix and dL/dcampos of each view,
  * which no other entry point returns (the reference treats the camera as a constant).  Called after
  * the views' render backward (gsr_backward*, gsr_backward_render or gsr_backward_render_views), before

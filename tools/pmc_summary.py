@@ -45,7 +45,9 @@ SHORT = {"preprocess_fwd_kernel": "preprocess_fwd", "preprocess_views_kernel": "
          "union_offsets_kernel": "union_plan", "union_rows_kernel": "union_plan",
          "rows_move_kernel": "rows_gather_scatter",
          # the camera gradient (GaussianRasterizer camera=, gsr_backward_camera_views)
-         "camera_bwd_views_kernel": "camera_bwd", "camera_bwd_finish_kernel": "camera_bwd"}
+         "camera_bwd_views_kernel": "camera_bwd", "camera_bwd_finish_kernel": "camera_bwd",
+         # the alpha output (GaussianRasterizer.forward's return_alpha)
+         "alpha_kernel": "alpha_output"}
 # the kernel bench.py --pmc-child launches between its warm-up and its counted steps
 MARKER = "spin_kernel"
 # operations made of several kernels (several dispatches per call)
